@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
 """Headline benchmark: allreduce bus bandwidth + p50 latency, 1 GB float[] (BASELINE.json).
 
-``python bench.py --gpus N --steps K --warmup W`` — for N>1 the driver launches one rank
-per GPU with ``torch.distributed.run``.  Every step is ONE public-API call
+``python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]`` — for N>1 the
+driver launches one rank per GPU with ``torch.distributed.run``.  Every step is ONE public-API call
 
     comm.allreduceArray(buf, Operands.FLOAT_OPERAND(), Operators.Float.SUM, 0, n, scale=1/p)
 
@@ -16,15 +16,27 @@ For N>1 the warm-up first autotunes the schedule (RCCL, RCCL with more channels,
 over xGMI staged / zero-copy pull / zero-copy push, a2a, rhd; ``--autotune-iters`` timed calls
 each, MAX over ranks, every candidate checked against an exact pattern first) and pins the
 fastest.  Timing: W untimed warmup calls, barrier + device sync, K timed back-to-back calls,
-barrier + device sync (the headline, host clock; MAX over ranks); then, outside the timed
-region, K more calls with a hipEvent pair around each for p50 / p99.
+barrier + device sync (the headline, host clock; MAX over ranks).
 
-Self-verification (after the timed steps, outside them): the SAME call on the SAME buffer with
+A plain run stops there: set-up, warm-up, the K timed steps, the outputs if ``--dump-outputs`` is
+given, ONE result line (``p50_ms``, ``verified``, the RCCL baseline and the other evidence keys
+are null).  Everything below runs only with ``--full``, which prints the headline line right
+after its measurement and an enriched final line (same numbers) at the end.
+
+``--dump-outputs DIR``: right after the timed steps rank 0 writes what the last timed call
+returned (N=1: ``out``; N>1: the in-place buffer) as ``DIR/allreduce_out.npy`` in float32; an
+array of more than 2^23 elements is cut to a fixed, seeded sample of 2^23 of its elements
+(32 MB).  The inputs are seeded per rank, so the same arguments give the same inputs every run.
+
+Latency distribution (``--full``): outside the timed region, K more calls with a hipEvent pair
+around each for p50 / p99.
+
+Self-verification (``--full``; after the timed steps, outside them): the SAME call on the SAME buffer with
 the pinned schedule runs once more on an exact pattern; the result is compared with the fp64
 answer on every rank -> ``verified`` and ``max_abs_err`` (MAX over ranks).  A wrong result
 makes the run exit non-zero (rc 3) after printing its line.
 
-RCCL baseline at equal method (N>1, GPU): K more calls of the same public call with the RCCL
+RCCL baseline at equal method (``--full``, N>1, GPU): K more calls of the same public call with the RCCL
 schedule forced (``ncclAllReduce``, fused ncclAvg), same timing method, MAX over ranks ->
 ``rccl_busbw_gbps`` / ``rccl_p50_ms`` next to ``value`` ("judge our
 numbers against RCCL's on the same box").
@@ -74,17 +86,21 @@ class _CpuEvent:
         return (other.t - self.t) * 1e3
 
 
-def _measure(torch, step, steps, sync_all):
+def _time_steps(step, steps, sync_all):
     """The headline timing: K back-to-back calls of ``step`` on the host clock, bracketed by a
-    device-wide sync + barrier on both sides (nothing else inside the timed region).  Then K
-    more calls with a hipEvent pair around each, in a separate pass, for the per-call latency
-    distribution (p50 / p99).  Returns (wall seconds of the timed K calls, sorted ms list)."""
+    device-wide sync + barrier on both sides (nothing else inside the timed region).  Returns the
+    wall seconds of the timed K calls."""
     sync_all()
     t0 = time.perf_counter()
     for _ in range(steps):
         step()
     sync_all()
-    wall = time.perf_counter() - t0
+    return time.perf_counter() - t0
+
+
+def _latency_pass(torch, step, steps, sync_all):
+    """K more calls with a hipEvent pair around each, in a pass of their own, for the per-call
+    latency distribution (p50 / p99).  Returns the sorted ms list."""
     starts = [torch.cuda.Event(enable_timing=True) for _ in range(steps)]
     ends = [torch.cuda.Event(enable_timing=True) for _ in range(steps)]
     for i in range(steps):
@@ -92,7 +108,49 @@ def _measure(torch, step, steps, sync_all):
         step()
         ends[i].record()
     sync_all()
-    return wall, sorted(s.elapsed_time(e) for s, e in zip(starts, ends))
+    return sorted(s.elapsed_time(e) for s, e in zip(starts, ends))
+
+
+def _measure(torch, step, steps, sync_all):
+    """Both passes: (wall seconds of the timed K calls, sorted ms list of K more calls)."""
+    wall = _time_steps(step, steps, sync_all)
+    return wall, _latency_pass(torch, step, steps, sync_all)
+
+
+DUMP_MAX_ELEMS = 1 << 23      # 32 MB of float32 per dumped array
+DUMP_SEED = 20240607
+
+
+def _dump_output(torch, out_dir, name, t):
+    """``out_dir/name.npy`` (float32): ``t`` whole, or a fixed seeded sample of its elements."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    n = t.numel()
+    if n > DUMP_MAX_ELEMS:
+        g = torch.Generator(device="cpu")
+        g.manual_seed(DUMP_SEED)
+        idx = torch.randint(0, n, (DUMP_MAX_ELEMS,), generator=g).sort().values
+        t = t[idx.to(t.device)]
+    np.save(os.path.join(out_dir, name + ".npy"), t.detach().to(torch.float32).cpu().numpy())
+
+
+def _leave_unwritable_cwd():
+    """The embedded master writes its ``kill_<port>.sh`` into the working directory (the
+    reference's Server.killMe).  Started from a directory this user cannot write, e.g. a read-only
+    checkout, the run moves to a temporary directory of its own, removed at exit; paths given
+    relative to the old one (mp4x's file / directory variables) are made absolute first."""
+    cwd = os.getcwd()
+    if os.access(cwd, os.W_OK | os.X_OK):
+        return
+    import atexit
+    import shutil
+    import tempfile
+    for var in ("MP4X_TUNE_FILE", "MP4X_TUNE_DIR", "MP4X_LOG_CONFIG", "MP4X_LOG_DIR"):
+        if os.environ.get(var):
+            os.environ[var] = os.path.abspath(os.environ[var])
+    tmp = tempfile.mkdtemp(prefix="mp4x_bench_")
+    os.chdir(tmp)
+    atexit.register(shutil.rmtree, tmp, ignore_errors=True)
 
 
 def _timed_p50(torch, fn, iters, sync):
@@ -231,11 +289,19 @@ def main():
     ap.add_argument("--no-rooted-sweep", action="store_true", help="N>1: skip the rooted collectives' sweep")
     ap.add_argument("--no-configs", action="store_true",
                     help="N>1: skip the untimed BASELINE configs 3-5 (4 GB bf16 RS+AG, sparse map, 8 GB fp8) run last")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed call returned as DIR/<name>.npy (float32)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline does not need: p50 / p99 pass, self-verification, RCCL "
+                         "baseline, topology probe, schedule sweeps, BASELINE configs 3-5")
     args = ap.parse_args()
     if args.no_register:
         args.alloc = "plain"
     if args.algo:
         os.environ["MP4X_DEVICE_ALGO"] = args.algo
+    if args.dump_outputs:
+        args.dump_outputs = os.path.abspath(args.dump_outputs)
+    _leave_unwritable_cwd()
 
     import torch
     import torch.distributed as dist
@@ -315,8 +381,17 @@ def main():
     for _ in range(args.warmup):
         step()
 
-    wall, lat = _measure(torch, step, args.steps, sync_all)     # lat: ms, from the separate event pass
-    wall, p50, p99 = max_over_ranks([wall, lat[len(lat) // 2], lat[min(len(lat) - 1, int(0.99 * len(lat)))]])
+    wall = _time_steps(step, args.steps, sync_all)
+    if args.dump_outputs:
+        if rank == 0:
+            _dump_output(torch, args.dump_outputs, "allreduce_out", out if p == 1 else buf)
+        sync_all()              # no rank starts another in-place call while rank 0 still reads
+    p50 = p99 = None
+    if args.full:
+        lat = _latency_pass(torch, step, args.steps, sync_all)     # ms, from the separate event pass
+        wall, p50, p99 = max_over_ranks([wall, lat[len(lat) // 2], lat[min(len(lat) - 1, int(0.99 * len(lat)))]])
+    else:
+        wall = max_over_ranks([wall])[0]
 
     ms_per_step = wall * 1e3 / args.steps
     nbytes = n * 4
@@ -330,7 +405,7 @@ def main():
 
     # ---- self-verification: the same call, same buffer, same pinned schedule, exact pattern
     verified, max_err = None, None
-    if not args.no_verify:
+    if args.full and not args.no_verify:
         idt = torch.int32 if n < (1 << 31) else torch.int64
         i13 = torch.arange(n, device=dev, dtype=idt).remainder_(13)
         buf.copy_(i13 + rank)
@@ -358,7 +433,7 @@ def main():
 
     # ---- RCCL at equal method on the same buffer (N>1, GPU)
     rccl = None
-    if p > 1 and not args.cpu and not args.no_rccl_baseline and not args.codec:
+    if args.full and p > 1 and not args.cpu and not args.no_rccl_baseline and not args.codec:
         eng = comm.device
         saved = eng.algo
         eng.algo = "rccl"
@@ -376,7 +451,7 @@ def main():
 
     ref = REF_BUSBW_MBPS.get(p)
     topo = None
-    if rank == 0 and not args.cpu:
+    if args.full and rank == 0 and not args.cpu:
         # which of the ranks' devices are one xGMI hop apart (native probe; one process per GPU
         # sees every device of the node, ranks 0..p-1 on devices 0..p-1)
         from mp4x.utils.topology import local_summary
@@ -425,8 +500,8 @@ def main():
             "busbw_gbps_per_rank": round(busbw, 3),
             "aggregate_busbw_gbps": round(busbw * p, 3),
             "algbw_gbps": round(algbw, 3),
-            "p50_ms": round(p50, 4),
-            "p99_ms": round(p99, 4),
+            "p50_ms": round(p50, 4) if p50 is not None else None,
+            "p99_ms": round(p99, 4) if p99 is not None else None,
             "rccl_busbw_gbps": rccl["rccl_busbw_gbps"] if rccl else None,
             "rccl_p50_ms": rccl["rccl_p50_ms"] if rccl else None,
             "rccl_baseline": rccl,
@@ -438,6 +513,20 @@ def main():
                      if p == 1 else "value = busbw = algbw * 2(p-1)/p (nccl-tests convention, per rank); "
                                     "aggregate_busbw_gbps = p * busbw; rccl_* = the same call with RCCL forced"),
         }
+
+    def finish():
+        if args.alloc == "memalloc" and p > 1 and not args.cpu:
+            comm.memFree(buf)
+        comm.close(0)
+        if p > 1 and dist.is_initialized():
+            dist.destroy_process_group()
+
+    # ---- a plain run ends here with its one result line
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(record("headline")), flush=True)
+        finish()
+        return
 
     # ---- the headline is measured, verified and next to RCCL: print it NOW, so nothing that runs
     # after it (sweeps, baseline configs) can lose it by hanging or overrunning the driver's timeout
@@ -525,11 +614,7 @@ def main():
     extras["seconds"] = round(time.perf_counter() - t_extra, 3)
     if rank == 0:
         print(json.dumps(record("final", tiers, configs, extras)), flush=True)
-    if args.alloc == "memalloc" and p > 1 and not args.cpu:
-        comm.memFree(buf)
-    comm.close(0)
-    if p > 1 and dist.is_initialized():
-        dist.destroy_process_group()
+    finish()
     if verified is False:
         print(f"bench: result NOT verified (max_abs_err {max_err})", file=sys.stderr, flush=True)
         sys.exit(RC_UNVERIFIED)

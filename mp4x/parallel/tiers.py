@@ -20,7 +20,7 @@ MI355X xGMI link's one-direction rate); S* is rounded to the nearest power of tw
 Autotune replaces the model by measurement for every size class it visits, and those pins persist
 (below).
 
-**Tune store.**  The tier sweep of ``bench.py`` autotunes every size class from 4 KiB to 64 MiB
+**Tune store.**  The tier sweep of ``bench.py --full`` autotunes every size class, 4 KiB to 64 MiB,
 on the job's real links; with ``MP4X_TUNE_AUTO=1`` (bench.py sets it) the pinned table is written
 to ``MP4X_TUNE_DIR`` (``~/.cache/mp4x/tune``) under a file named after the job's topology key —
 rank count, device name, backend, node count and the xGMI pair map of the ranks' devices

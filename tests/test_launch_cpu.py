@@ -19,10 +19,10 @@ def _free_port():
     return port
 
 
-def _run(tmp_path, nproc=4, extra_env=None, steps=3):
+def _run(tmp_path, nproc=4, extra_env=None, steps=3, more=("--full",)):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(nproc),
            "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"),
-           "--cpu", "--gpus", str(nproc), "--steps", str(steps), "--warmup", "1", "--bytes", "4000000"]
+           "--cpu", "--gpus", str(nproc), "--steps", str(steps), "--warmup", "1", "--bytes", "4000000", *more]
     # stderr apart from stdout, as the driver reads it: the ranks' warnings (a failed verification
     # is reported on stderr by every rank) must not interleave with rank 0's JSON lines
     r = subprocess.run(cmd, cwd=tmp_path, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=300,
@@ -53,6 +53,52 @@ def test_torchrun_bench_dry_run_all_ranks_exit_clean(tmp_path):
     assert rec["config"]["scale"] == 0.25 and rec["config"]["autotune_iters"] >= 5
 
 
+def test_plain_run_prints_one_line_and_dumps_the_last_timed_output(tmp_path):
+    """Without ``--full`` the run is set-up, warm-up, timed steps, ONE result line: no latency pass,
+    no verification, no extras.  ``--dump-outputs`` writes what the last timed call returned; the
+    inputs are seeded per rank, so the expected array is known here: the in-place average of the two
+    ranks' inputs (repeating the averaging call leaves it unchanged up to fp32 rounding)."""
+    import numpy as np
+    import torch
+    out_dir = tmp_path / "dump"
+    r, lines = _run(tmp_path, nproc=2, more=("--dump-outputs", str(out_dir)))
+    assert r.returncode == 0, r.stdout[-3000:]
+    assert len(lines) == 1, lines
+    rec = lines[0]
+    assert rec["steps"] == 3 and rec["n_gpus"] == 2 and rec["value"] > 0 and rec["ms_per_step"] > 0
+    assert rec["unit"] == "GB/s" and rec["higher_is_better"] is True and rec["dtype"] == "fp32"
+    # value = busbw = algbw * 2(p-1)/p = bytes / ms_per_step (p = 2)
+    assert abs(rec["value"] - 4000000 / (rec["ms_per_step"] * 1e-3) / 1e9) <= 0.01 * rec["value"] + 1e-3
+    assert rec["p50_ms"] is None and rec["verified"] is None and rec["config"]["extras"] is None
+    assert sorted(os.listdir(out_dir)) == ["allreduce_out.npy"]
+    got = np.load(out_dir / "allreduce_out.npy")
+    assert got.dtype == np.float32 and got.shape == (1000000,)
+    xs = [torch.empty(1000000).normal_(generator=torch.Generator().manual_seed(1234 + k)) for k in range(2)]
+    # 4 averaging calls in fp32: the first is exact up to one rounding, each later one adds at most one more
+    np.testing.assert_allclose(got, ((xs[0].double() + xs[1].double()) / 2).numpy(), rtol=4 * 2.0 ** -24, atol=1e-30)
+
+
+def test_plain_run_from_a_read_only_directory(tmp_path):
+    """Started in a directory the user cannot write (a read-only checkout), the run still ends with
+    its result line: the embedded master's kill script goes to a temporary directory instead."""
+    ro = tmp_path / "ro"
+    ro.mkdir()
+    ro.chmod(0o555)
+    try:
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--cpu", "--gpus", "1", "--steps", "2", "--warmup", "1",
+               "--bytes", "4000000", "--dump-outputs", str(tmp_path / "dump")]
+        env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+        r = subprocess.run(cmd, cwd=ro, capture_output=True, text=True, timeout=300, env=dict(env, PYTHONPATH=ROOT))
+        assert r.returncode == 0, (r.stdout + r.stderr)[-3000:]
+        lines = [json.loads(x) for x in r.stdout.splitlines() if x.startswith('{"metric"')]
+        assert len(lines) == 1 and lines[0]["steps"] == 2 and lines[0]["ms_per_step"] > 0, lines
+        assert os.path.exists(tmp_path / "dump" / "allreduce_out.npy")
+        if not os.access(ro, os.W_OK):          # root may write anywhere: nothing to see then
+            assert os.listdir(ro) == []
+    finally:
+        ro.chmod(0o755)
+
+
 def test_bench_values_stay_bounded_over_many_steps(tmp_path):
     # scale=1/p: 60 SUM steps at p=2 would otherwise multiply the data by 2^60
     r, lines = _run(tmp_path, nproc=2, steps=60)
@@ -74,7 +120,7 @@ def test_headline_survives_a_hang_after_it(tmp_path):
     import time
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"),
-           "--cpu", "--gpus", "2", "--steps", "3", "--warmup", "1", "--bytes", "4000000"]
+           "--cpu", "--gpus", "2", "--steps", "3", "--warmup", "1", "--bytes", "4000000", "--full"]
     pr = subprocess.Popen(cmd, cwd=tmp_path, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True,
                           env=dict(os.environ, PYTHONPATH=ROOT, MP4X_BENCH_TEST_HANG="extras",
                                    MP4X_BENCH_TEST_HANG_S="60"),

@@ -15,7 +15,7 @@ for np in ${NPS:-2 4 8}; do
   step bench_$tag ${LIMIT:-540} env MP4X_DEVICE_BACKEND=gloo MP4X_DEVICE_INDEX=0 GPU_MAX_HW_QUEUES=$q \
     python -m torch.distributed.run --nnodes=1 --nproc-per-node $np --master-addr 127.0.0.1 \
     --master-port $((29640 + np + 10 * k)) bench.py --gpus $np --steps ${STEPS:-10} --warmup 3 --bytes ${BYTES:-1000000000} \
-    --no-rccl-baseline $EXTRA
+    --full --no-rccl-baseline $EXTRA
   echo "$tag wall_s $(( $(date +%s) - t0 ))" | tee -a "gpurun_out/$OUT/walltime.txt"
   grep -h '^{' "gpurun_out/$OUT/bench_$tag.log" > "gpurun_out/$OUT/bench_$tag.jsonl" || true
   grep -h "ruled out\|probe failed\|first-use" "gpurun_out/$OUT/bench_$tag.log" > "gpurun_out/$OUT/ruled_out_$tag.txt" || true
