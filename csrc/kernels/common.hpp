@@ -3,6 +3,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #include "mp4x/ops.h"
 
 namespace mp4x {
@@ -141,6 +143,168 @@ __device__ __forceinline__ typename Elem<DT>::A combine(typename Elem<DT>::A a, 
     bool keep = (OP == MP4X_IMAXLOC) ? (va >= vb) : (va <= vb);
     return keep ? a : b;
   }
+}
+
+// ---------------------------------------------------------------- 16-byte vectors of elements
+// A packed value V (a 16-byte u32x4, or one storage element S) <-> its W accumulators.
+template <int DT, typename V, int W>
+__device__ __forceinline__ void unpack(const V& v, typename Elem<DT>::A (&a)[W]) {
+  using E = Elem<DT>;
+  typename E::S s[W];
+  static_assert(sizeof(s) == sizeof(V), "W elements fill V");
+  __builtin_memcpy(s, &v, sizeof(V));
+#pragma unroll
+  for (int j = 0; j < W; ++j) a[j] = E::load(s[j]);
+}
+template <int DT, typename V, int W>
+__device__ __forceinline__ V pack(const typename Elem<DT>::A (&a)[W]) {
+  using E = Elem<DT>;
+  typename E::S s[W];
+  static_assert(sizeof(s) == sizeof(V), "W elements fill V");
+#pragma unroll
+  for (int j = 0; j < W; ++j) s[j] = E::store(a[j]);
+  V v;
+  __builtin_memcpy(&v, s, sizeof(V));
+  return v;
+}
+
+// acc[j] = combine(acc[j], element j of v): one more packed value folded into the accumulators
+// (element by element: convert, combine — the order the kernels were tuned with).
+template <int DT, int OP, typename V, int W>
+__device__ __forceinline__ void fold_in(typename Elem<DT>::A (&acc)[W], const V& v) {
+  using E = Elem<DT>;
+  typename E::S s[W];
+  static_assert(sizeof(s) == sizeof(V), "W elements fill V");
+  __builtin_memcpy(s, &v, sizeof(V));
+#pragma unroll
+  for (int j = 0; j < W; ++j) acc[j] = combine<DT, OP>(acc[j], E::load(s[j]));
+}
+
+// Combine of NR 16-byte vectors (rank order: r[0] first, deterministic), then the optional
+// fused scale (float dtypes, a wave-uniform branch; 1.0 = plain reduction).  The fold of K1 and of
+// every IPC kernel.  It stays one body, not unpack + fold_in + pack: written through them the
+// compiler orders and allocates the IPC kernels differently (the same arithmetic), and their
+// register budgets are part of the library (mp4x/_native/ipc_kernel_resources.json).
+template <int DT, int OP, int NR>
+__device__ __forceinline__ u32x4 fold_vec(const u32x4 (&r)[NR], float scale = 1.0f) {
+  using E = Elem<DT>;
+  using S = typename E::S;
+  using A = typename E::A;
+  constexpr int W = 16 / sizeof(S);
+  S s[W];
+  __builtin_memcpy(s, &r[0], 16);
+  A acc[W];
+#pragma unroll
+  for (int j = 0; j < W; ++j) acc[j] = E::load(s[j]);
+#pragma unroll
+  for (int k = 1; k < NR; ++k) {
+    S x[W];
+    __builtin_memcpy(x, &r[k], 16);
+#pragma unroll
+    for (int j = 0; j < W; ++j) acc[j] = combine<DT, OP>(acc[j], E::load(x[j]));
+  }
+  if constexpr (is_float_dt<DT>()) {
+    if (scale != 1.0f) {
+#pragma unroll
+      for (int j = 0; j < W; ++j) acc[j] = acc[j] * (A)scale;
+    }
+  }
+#pragma unroll
+  for (int j = 0; j < W; ++j) s[j] = E::store(acc[j]);
+  u32x4 o;
+  __builtin_memcpy(&o, s, 16);
+  return o;
+}
+
+// out[i] = the combine of element i of NIN inputs, in input order (scalar tails, unaligned operands).
+template <int DT, int OP, int NIN>
+__device__ __forceinline__ void fold_elem(void* out, const void* const (&ins)[NIN], int64_t i) {
+  using E = Elem<DT>;
+  using S = typename E::S;
+  typename E::A acc = E::load(reinterpret_cast<const S*>(ins[0])[i]);
+#pragma unroll
+  for (int k = 1; k < NIN; ++k) acc = combine<DT, OP>(acc, E::load(reinterpret_cast<const S*>(ins[k])[i]));
+  reinterpret_cast<S*>(out)[i] = E::store(acc);
+}
+
+// ---------------------------------------------------------------- host-side dispatch
+// Every runtime (dtype, op) pair becomes template arguments here and nowhere else: a new dtype is
+// a case of with_dtype (and an Elem), a new operator an entry of the op lists (and of op_valid /
+// combine).
+template <int V> using IntC = std::integral_constant<int, V>;
+
+// f(IntC<DT>{}) for a runtime dtype code; `unknown` for a code outside the table.
+template <typename F> inline int with_dtype(int dtype, F&& f, int unknown = MP4X_E_UNSUPPORTED) {
+  switch (dtype) {
+    case MP4X_F64: return f(IntC<MP4X_F64>{});
+    case MP4X_F32: return f(IntC<MP4X_F32>{});
+    case MP4X_I64: return f(IntC<MP4X_I64>{});
+    case MP4X_I32: return f(IntC<MP4X_I32>{});
+    case MP4X_I16: return f(IntC<MP4X_I16>{});
+    case MP4X_I8: return f(IntC<MP4X_I8>{});
+    case MP4X_BF16: return f(IntC<MP4X_BF16>{});
+    case MP4X_F16: return f(IntC<MP4X_F16>{});
+    case MP4X_U8: return f(IntC<MP4X_U8>{});
+    default: return unknown;
+  }
+}
+
+// The operator lists of the kernel families.
+template <int... OPS> struct OpList {};
+// the reference's operator table (MP4X_FIRST is a sparse-merge rule, not a collective operator):
+// K1 and the IPC runtime-op kernels
+using TableOps = OpList<MP4X_SUM, MP4X_MAX, MP4X_MIN, MP4X_PROD, MP4X_BAND, MP4X_BOR, MP4X_BXOR, MP4X_FMAXLOC,
+                        MP4X_FMINLOC, MP4X_IMAXLOC, MP4X_IMINLOC>;
+// row reductions of the hash / dense reduce-by-key ...
+using RowOps = OpList<MP4X_SUM, MP4X_MAX, MP4X_MIN, MP4X_PROD, MP4X_BAND, MP4X_BOR, MP4X_BXOR>;
+// ... and of the segmented reduce, which also serves the FIRST rule (K8)
+using RowOpsFirst = OpList<MP4X_SUM, MP4X_MAX, MP4X_MIN, MP4X_PROD, MP4X_BAND, MP4X_BOR, MP4X_BXOR, MP4X_FIRST>;
+
+// f(IntC<OP>{}) for a runtime op code of the list; MP4X_E_UNSUPPORTED for a listed op that is no
+// operator of DT (op_valid), `unlisted` for a code outside the list.
+template <int DT, int... OPS, typename F> inline int with_op_of(OpList<OPS...>, int op, int unlisted, F&& f) {
+  int rc = unlisted;
+  auto on = [&](auto opc) {
+    constexpr int OP = decltype(opc)::value;
+    if (op != OP) return false;
+    if constexpr (op_valid<DT, OP>()) rc = f(opc);
+    else rc = MP4X_E_UNSUPPORTED;
+    return true;
+  };
+  (void)(on(IntC<OPS>{}) || ...);
+  return rc;
+}
+
+// 0 when `op` is in the list and an operator of `dtype`, else MP4X_E_UNSUPPORTED.
+template <typename Ops> inline int pair_supported(Ops ops, int dtype, int op) {
+  return with_dtype(dtype, [&](auto dtc) {
+    return with_op_of<decltype(dtc)::value>(ops, op, MP4X_E_UNSUPPORTED, [](auto) { return 0; });
+  });
+}
+
+// f(IntC<N>{}) for a count LO..8 (K1's fan-in, the IPC kernels' rank count), else MP4X_E_BADARG.
+template <int LO, typename F> inline int with_count(int n, F&& f) {
+  switch (n) {
+    case 1:
+      if constexpr (LO <= 1) return f(IntC<1>{});
+      return MP4X_E_BADARG;
+    case 2: return f(IntC<2>{});
+    case 3: return f(IntC<3>{});
+    case 4: return f(IntC<4>{});
+    case 5: return f(IntC<5>{});
+    case 6: return f(IntC<6>{});
+    case 7: return f(IntC<7>{});
+    case 8: return f(IntC<8>{});
+    default: return MP4X_E_BADARG;
+  }
+}
+
+// Bytes per element of a dtype code (0: unknown), and whether it is a float dtype.
+inline int elem_size(int dtype) {
+  return with_dtype(dtype, [](auto dtc) { return (int)sizeof(typename Elem<decltype(dtc)::value>::S); }, 0);
+}
+inline bool float_dtype(int dtype) {
+  return with_dtype(dtype, [](auto dtc) { return (int)is_float_dt<decltype(dtc)::value>(); }, 0) != 0;
 }
 
 }  // namespace mp4x

@@ -24,10 +24,7 @@ template <int NIN> struct InPtrs { const void* p[NIN]; };
 template <int DT, int OP, int NIN>
 __global__ __launch_bounds__(kBlock) void k_reduce_vec(void* __restrict__ out_, InPtrs<NIN> ins,
                                                        int64_t nvec, int64_t n) {
-  using E = Elem<DT>;
-  using S = typename E::S;
-  using A = typename E::A;
-  constexpr int W = 16 / sizeof(S);
+  constexpr int W = 16 / sizeof(typename Elem<DT>::S);
   const int64_t nthr = (int64_t)gridDim.x * kBlock;
   const int64_t tid = (int64_t)blockIdx.x * kBlock + threadIdx.x;
   u32x4* out = reinterpret_cast<u32x4*>(out_);
@@ -35,44 +32,21 @@ __global__ __launch_bounds__(kBlock) void k_reduce_vec(void* __restrict__ out_, 
   for (int64_t v = tid; v < nvec; v += 2 * nthr) {
     const int64_t v1 = v + nthr;
     const bool two = v1 < nvec;
-    u32x4 r0[NIN], r1[NIN];
+    u32x4 r[2][NIN];
 #pragma unroll
     for (int k = 0; k < NIN; ++k) {
-      r0[k] = reinterpret_cast<const u32x4*>(ins.p[k])[v];
-      if (two) r1[k] = reinterpret_cast<const u32x4*>(ins.p[k])[v1];
+      r[0][k] = reinterpret_cast<const u32x4*>(ins.p[k])[v];
+      if (two) r[1][k] = reinterpret_cast<const u32x4*>(ins.p[k])[v1];
     }
 #pragma unroll
     for (int u = 0; u < 2; ++u) {
       if (u == 1 && !two) break;
-      u32x4* r = u ? r1 : r0;
-      S acc_s[W];
-      __builtin_memcpy(acc_s, &r[0], 16);
-      A acc[W];
-#pragma unroll
-      for (int j = 0; j < W; ++j) acc[j] = E::load(acc_s[j]);
-#pragma unroll
-      for (int k = 1; k < NIN; ++k) {
-        S x[W];
-        __builtin_memcpy(x, &r[k], 16);
-#pragma unroll
-        for (int j = 0; j < W; ++j) acc[j] = combine<DT, OP>(acc[j], E::load(x[j]));
-      }
-#pragma unroll
-      for (int j = 0; j < W; ++j) acc_s[j] = E::store(acc[j]);
-      u32x4 o;
-      __builtin_memcpy(&o, acc_s, 16);
-      out[u ? v1 : v] = o;
+      out[u ? v1 : v] = fold_vec<DT, OP>(r[u]);
     }
   }
   // scalar tail (< W elements)
   const int64_t base = nvec * W;
-  if (tid < n - base) {
-    const int64_t i = base + tid;
-    A acc = E::load(reinterpret_cast<const S*>(ins.p[0])[i]);
-#pragma unroll
-    for (int k = 1; k < NIN; ++k) acc = combine<DT, OP>(acc, E::load(reinterpret_cast<const S*>(ins.p[k])[i]));
-    reinterpret_cast<S*>(out_)[i] = E::store(acc);
-  }
+  if (tid < n - base) fold_elem<DT, OP>(out_, ins.p, base + tid);
 }
 
 // Tile variant: block b owns vectors [b*kBlock*U, (b+1)*kBlock*U); lane t handles
@@ -93,10 +67,7 @@ __device__ __forceinline__ void st(T* p, T v) {
 template <int DT, int OP, int NIN, int U, bool NT>
 __global__ __launch_bounds__(kBlock) void k_reduce_tile(void* __restrict__ out_, InPtrs<NIN> ins, int64_t nvec,
                                                         int64_t n) {
-  using E = Elem<DT>;
-  using S = typename E::S;
-  using A = typename E::A;
-  constexpr int W = 16 / sizeof(S);
+  constexpr int W = 16 / sizeof(typename Elem<DT>::S);
   u32x4* out = reinterpret_cast<u32x4*>(out_);
   // grid-stride over tiles when the launch caps the grid (MP4X_K1_GRID).  Default: no cap, one
   // tile per block — a capped grid measured no better for NIN = 1-2 and 20% slower for NIN >= 4
@@ -111,57 +82,21 @@ __global__ __launch_bounds__(kBlock) void k_reduce_tile(void* __restrict__ out_,
 #pragma unroll
       for (int u = 0; u < U; ++u) r[u][k] = ld<u32x4, NT>(reinterpret_cast<const u32x4*>(ins.p[k]) + base + u * kBlock);
 #pragma unroll
-    for (int u = 0; u < U; ++u) {
-      S a_s[W];
-      __builtin_memcpy(a_s, &r[u][0], 16);
-      A acc[W];
-#pragma unroll
-      for (int j = 0; j < W; ++j) acc[j] = E::load(a_s[j]);
-#pragma unroll
-      for (int k = 1; k < NIN; ++k) {
-        S x[W];
-        __builtin_memcpy(x, &r[u][k], 16);
-#pragma unroll
-        for (int j = 0; j < W; ++j) acc[j] = combine<DT, OP>(acc[j], E::load(x[j]));
-      }
-#pragma unroll
-      for (int j = 0; j < W; ++j) a_s[j] = E::store(acc[j]);
-      u32x4 o;
-      __builtin_memcpy(&o, a_s, 16);
-      st<u32x4, NT>(out + base + u * kBlock, o);
-    }
-  } else {
+    for (int u = 0; u < U; ++u) st<u32x4, NT>(out + base + u * kBlock, fold_vec<DT, OP>(r[u]));
+  } else {   // the partial last tile
     for (int u = 0; u < U; ++u) {
       const int64_t v = base + (int64_t)u * kBlock;
       if (v >= nvec) break;
-      S a_s[W];
-      u32x4 t0 = reinterpret_cast<const u32x4*>(ins.p[0])[v];
-      __builtin_memcpy(a_s, &t0, 16);
-      A acc[W];
-      for (int j = 0; j < W; ++j) acc[j] = E::load(a_s[j]);
-      for (int k = 1; k < NIN; ++k) {
-        S x[W];
-        u32x4 tk = reinterpret_cast<const u32x4*>(ins.p[k])[v];
-        __builtin_memcpy(x, &tk, 16);
-        for (int j = 0; j < W; ++j) acc[j] = combine<DT, OP>(acc[j], E::load(x[j]));
-      }
-      for (int j = 0; j < W; ++j) a_s[j] = E::store(acc[j]);
-      u32x4 o;
-      __builtin_memcpy(&o, a_s, 16);
-      out[v] = o;
+      typename Elem<DT>::A acc[W];              // one input at a time: few registers, off the hot path
+      unpack<DT>(reinterpret_cast<const u32x4*>(ins.p[0])[v], acc);
+      for (int k = 1; k < NIN; ++k) fold_in<DT, OP>(acc, reinterpret_cast<const u32x4*>(ins.p[k])[v]);
+      out[v] = pack<DT, u32x4>(acc);
     }
   }
   }
   // scalar tail handled by block 0
-  if (blockIdx.x == 0) {
-    const int64_t tb = nvec * W;
-    if ((int64_t)threadIdx.x < n - tb) {
-      const int64_t i = tb + threadIdx.x;
-      A acc = E::load(reinterpret_cast<const S*>(ins.p[0])[i]);
-      for (int k = 1; k < NIN; ++k) acc = combine<DT, OP>(acc, E::load(reinterpret_cast<const S*>(ins.p[k])[i]));
-      reinterpret_cast<S*>(out_)[i] = E::store(acc);
-    }
-  }
+  const int64_t tb = nvec * W;
+  if (blockIdx.x == 0 && (int64_t)threadIdx.x < n - tb) fold_elem<DT, OP>(out_, ins.p, tb + threadIdx.x);
 }
 
 static int64_t g_k1_grid = -1;
@@ -192,22 +127,24 @@ static int k1_variant() {
 
 template <int DT, int OP, int NIN>
 __global__ __launch_bounds__(kBlock) void k_reduce_scalar(void* __restrict__ out_, InPtrs<NIN> ins, int64_t n) {
-  using E = Elem<DT>;
-  using S = typename E::S;
-  using A = typename E::A;
   const int64_t nthr = (int64_t)gridDim.x * kBlock;
-  for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += nthr) {
-    A acc = E::load(reinterpret_cast<const S*>(ins.p[0])[i]);
-#pragma unroll
-    for (int k = 1; k < NIN; ++k) acc = combine<DT, OP>(acc, E::load(reinterpret_cast<const S*>(ins.p[k])[i]));
-    reinterpret_cast<S*>(out_)[i] = E::store(acc);
-  }
+  for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += nthr) fold_elem<DT, OP>(out_, ins.p, i);
+}
+
+// One tile of U vectors per lane and block; MP4X_K1_GRID caps the grid (then grid-strided).
+template <int DT, int OP, int NIN, int U, bool NT>
+static void launch_tile(void* out, const InPtrs<NIN>& p, int64_t nvec, int64_t n, hipStream_t st) {
+  const int64_t per_block = (int64_t)kBlock * U;
+  int64_t g = (nvec + per_block - 1) / per_block;
+  if (g < 1) g = 1;
+  const int64_t cap = k1_grid_for(NIN);
+  if (cap > 0 && g > cap) g = cap;
+  hipLaunchKernelGGL((k_reduce_tile<DT, OP, NIN, U, NT>), dim3((unsigned)g), dim3(kBlock), 0, st, out, p, nvec, n);
 }
 
 template <int DT, int OP, int NIN>
 static int launch_nin(void* out, const void* const* ins, int64_t n, hipStream_t st) {
-  using S = typename Elem<DT>::S;
-  constexpr int W = 16 / sizeof(S);
+  constexpr int W = 16 / sizeof(typename Elem<DT>::S);
   InPtrs<NIN> p;
   bool aligned = ((uintptr_t)out % 16) == 0;
   for (int k = 0; k < NIN; ++k) {
@@ -215,41 +152,29 @@ static int launch_nin(void* out, const void* const* ins, int64_t n, hipStream_t 
     aligned = aligned && ((uintptr_t)ins[k] % 16) == 0;
   }
   if (aligned) {
-    int64_t nvec = n / W;
+    const int64_t nvec = n / W;
+    // U vectors per lane: keep ~4-8 16-B loads in flight per lane (variant 3, U2: ~8-16)
+    // measured (tools/bench_kernels.py --variants, profiles/r1/k1_variants2.txt): 4 vectors per
+    // lane for 1-2 inputs (6.1 / 6.4 TB/s), 1 vector per lane from 4 inputs up
+    constexpr int U = NIN >= 4 ? 1 : (NIN == 3 ? 2 : 4);
+    constexpr int U2 = NIN >= 8 ? 1 : (NIN >= 4 ? 2 : 4);
     // the A/B variants (MP4X_K1_VARIANT, tools/bench_kernels.py --variants) are built for f32
     // only: every other dtype runs the default tile + nontemporal kernel (a quarter of the
     // template instantiations, which dominated the library's build time)
-    const int var = DT == MP4X_F32 ? k1_variant() : 2;
-    if constexpr (DT != MP4X_F32) {
-      constexpr int U = NIN >= 4 ? 1 : (NIN == 3 ? 2 : 4);
-      int64_t per_block = (int64_t)kBlock * U;
-      int64_t g = (nvec + per_block - 1) / per_block;
-      if (g < 1) g = 1;
-      const int64_t cap = k1_grid_for(NIN);
-      if (cap > 0 && g > cap) g = cap;
-      hipLaunchKernelGGL((k_reduce_tile<DT, OP, NIN, U, true>), dim3((unsigned)g), dim3(kBlock), 0, st, out, p, nvec, n);
-      (void)var;
-    } else if (var == 0) {
-      int g = grid_for(nvec > 0 ? nvec : 1, 2);
-      hipLaunchKernelGGL((k_reduce_vec<DT, OP, NIN>), dim3(g), dim3(kBlock), 0, st, out, p, nvec, n);
+    if constexpr (DT == MP4X_F32) {
+      const int var = k1_variant();
+      if (var == 0) {
+        int g = grid_for(nvec > 0 ? nvec : 1, 2);
+        hipLaunchKernelGGL((k_reduce_vec<DT, OP, NIN>), dim3(g), dim3(kBlock), 0, st, out, p, nvec, n);
+      } else if (var == 1) {
+        launch_tile<DT, OP, NIN, U, false>(out, p, nvec, n, st);
+      } else if (var == 3) {
+        launch_tile<DT, OP, NIN, U2, true>(out, p, nvec, n, st);
+      } else {
+        launch_tile<DT, OP, NIN, U, true>(out, p, nvec, n, st);
+      }
     } else {
-      // U vectors per lane: keep ~4-8 16-B loads in flight per lane (variant 3: ~8-16)
-      // measured (tools/bench_kernels.py --variants, profiles/r1/k1_variants2.txt): 4 vectors per
-      // lane for 1-2 inputs (6.1 / 6.4 TB/s), 1 vector per lane from 4 inputs up
-      constexpr int U = NIN >= 4 ? 1 : (NIN == 3 ? 2 : 4);
-      constexpr int U2 = NIN >= 8 ? 1 : (NIN >= 4 ? 2 : 4);
-      const int u = var == 3 ? U2 : U;
-      int64_t per_block = (int64_t)kBlock * u;
-      int64_t g = (nvec + per_block - 1) / per_block;
-      if (g < 1) g = 1;
-      const int64_t cap = k1_grid_for(NIN);
-      if (cap > 0 && g > cap) g = cap;
-      if (var == 1)
-        hipLaunchKernelGGL((k_reduce_tile<DT, OP, NIN, U, false>), dim3((unsigned)g), dim3(kBlock), 0, st, out, p, nvec, n);
-      else if (var == 3)
-        hipLaunchKernelGGL((k_reduce_tile<DT, OP, NIN, U2, true>), dim3((unsigned)g), dim3(kBlock), 0, st, out, p, nvec, n);
-      else
-        hipLaunchKernelGGL((k_reduce_tile<DT, OP, NIN, U, true>), dim3((unsigned)g), dim3(kBlock), 0, st, out, p, nvec, n);
+      launch_tile<DT, OP, NIN, U, true>(out, p, nvec, n, st);
     }
   } else {
     int g = grid_for(n, 4);
@@ -258,66 +183,16 @@ static int launch_nin(void* out, const void* const* ins, int64_t n, hipStream_t 
   return (int)hipGetLastError();
 }
 
-template <int DT, int OP>
-static int launch_op(void* out, const void* const* ins, int nin, int64_t n, hipStream_t st) {
-  if constexpr (!op_valid<DT, OP>()) {
-    return MP4X_E_UNSUPPORTED;
-  } else {
-    switch (nin) {
-      case 1: return launch_nin<DT, OP, 1>(out, ins, n, st);
-      case 2: return launch_nin<DT, OP, 2>(out, ins, n, st);
-      case 3: return launch_nin<DT, OP, 3>(out, ins, n, st);
-      case 4: return launch_nin<DT, OP, 4>(out, ins, n, st);
-      case 5: return launch_nin<DT, OP, 5>(out, ins, n, st);
-      case 6: return launch_nin<DT, OP, 6>(out, ins, n, st);
-      case 7: return launch_nin<DT, OP, 7>(out, ins, n, st);
-      case 8: return launch_nin<DT, OP, 8>(out, ins, n, st);
-      default: return MP4X_E_BADARG;
-    }
-  }
-}
-
-template <int DT>
-static int launch_dt(int op, void* out, const void* const* ins, int nin, int64_t n, hipStream_t st) {
-  switch (op) {
-    case MP4X_SUM: return launch_op<DT, MP4X_SUM>(out, ins, nin, n, st);
-    case MP4X_MAX: return launch_op<DT, MP4X_MAX>(out, ins, nin, n, st);
-    case MP4X_MIN: return launch_op<DT, MP4X_MIN>(out, ins, nin, n, st);
-    case MP4X_PROD: return launch_op<DT, MP4X_PROD>(out, ins, nin, n, st);
-    case MP4X_BAND: return launch_op<DT, MP4X_BAND>(out, ins, nin, n, st);
-    case MP4X_BOR: return launch_op<DT, MP4X_BOR>(out, ins, nin, n, st);
-    case MP4X_BXOR: return launch_op<DT, MP4X_BXOR>(out, ins, nin, n, st);
-    case MP4X_FMAXLOC: return launch_op<DT, MP4X_FMAXLOC>(out, ins, nin, n, st);
-    case MP4X_FMINLOC: return launch_op<DT, MP4X_FMINLOC>(out, ins, nin, n, st);
-    case MP4X_IMAXLOC: return launch_op<DT, MP4X_IMAXLOC>(out, ins, nin, n, st);
-    case MP4X_IMINLOC: return launch_op<DT, MP4X_IMINLOC>(out, ins, nin, n, st);
-    default: return MP4X_E_BADARG;
-  }
-}
-
+// One launch of up to MP4X_MAX_NIN inputs.  An unknown dtype or an op outside the operator table
+// is a bad argument; a pair the table does not hold is unsupported.
 static int dispatch(int dtype, int op, void* out, const void* const* ins, int nin, int64_t n, hipStream_t st) {
-  switch (dtype) {
-    case MP4X_F64: return launch_dt<MP4X_F64>(op, out, ins, nin, n, st);
-    case MP4X_F32: return launch_dt<MP4X_F32>(op, out, ins, nin, n, st);
-    case MP4X_I64: return launch_dt<MP4X_I64>(op, out, ins, nin, n, st);
-    case MP4X_I32: return launch_dt<MP4X_I32>(op, out, ins, nin, n, st);
-    case MP4X_I16: return launch_dt<MP4X_I16>(op, out, ins, nin, n, st);
-    case MP4X_I8: return launch_dt<MP4X_I8>(op, out, ins, nin, n, st);
-    case MP4X_U8: return launch_dt<MP4X_U8>(op, out, ins, nin, n, st);
-    case MP4X_BF16: return launch_dt<MP4X_BF16>(op, out, ins, nin, n, st);
-    case MP4X_F16: return launch_dt<MP4X_F16>(op, out, ins, nin, n, st);
-    default: return MP4X_E_BADARG;
-  }
-}
-
-static int elem_size(int dtype) {
-  switch (dtype) {
-    case MP4X_F64: case MP4X_I64: return 8;
-    case MP4X_F32: case MP4X_I32: return 4;
-    case MP4X_I16: case MP4X_BF16: case MP4X_F16: return 2;
-    case MP4X_I8: case MP4X_U8: return 1;
-    default: return 0;
-  }
+  return with_dtype(dtype, [&](auto dtc) {
+    constexpr int DT = decltype(dtc)::value;
+    return with_op_of<DT>(TableOps{}, op, MP4X_E_BADARG, [&](auto opc) {
+      constexpr int OP = decltype(opc)::value;
+      return with_count<1>(nin, [&](auto nc) { return launch_nin<DT, OP, decltype(nc)::value>(out, ins, n, st); });
+    });
+  }, MP4X_E_BADARG);
 }
 
 // ---------------------------------------------------------------- scale (averaging)
@@ -338,13 +213,11 @@ __global__ __launch_bounds__(kBlock) void k_scale(void* out_, const void* in_, d
     const u32x4* vin = reinterpret_cast<const u32x4*>(in);
     u32x4* vout = reinterpret_cast<u32x4*>(out);
     for (int64_t v = t0; v < nv; v += nthr) {
-      u32x4 t = __builtin_nontemporal_load(vin + v);
-      S x[W];
-      __builtin_memcpy(x, &t, 16);
+      A x[W];
+      unpack<DT>(__builtin_nontemporal_load(vin + v), x);
 #pragma unroll
-      for (int j = 0; j < W; ++j) x[j] = E::store(E::load(x[j]) * s);
-      __builtin_memcpy(&t, x, 16);
-      __builtin_nontemporal_store(t, vout + v);
+      for (int j = 0; j < W; ++j) x[j] = x[j] * s;
+      __builtin_nontemporal_store(pack<DT, u32x4>(x), vout + v);
     }
     done = nv * W;
   }
@@ -388,15 +261,15 @@ extern "C" int mp4x_reduce_strided(int dtype, int op, void* out, const void* bas
 extern "C" int mp4x_scale(int dtype, void* out, const void* in, double scale, int64_t n, void* stream) {
   if (n <= 0) return 0;
   hipStream_t st = (hipStream_t)stream;
-  int g = grid_for(n, 4);
-  switch (dtype) {
-    case MP4X_F64: hipLaunchKernelGGL(k_scale<MP4X_F64>, dim3(g), dim3(kBlock), 0, st, out, in, scale, n); break;
-    case MP4X_F32: hipLaunchKernelGGL(k_scale<MP4X_F32>, dim3(g), dim3(kBlock), 0, st, out, in, scale, n); break;
-    case MP4X_BF16: hipLaunchKernelGGL(k_scale<MP4X_BF16>, dim3(g), dim3(kBlock), 0, st, out, in, scale, n); break;
-    case MP4X_F16: hipLaunchKernelGGL(k_scale<MP4X_F16>, dim3(g), dim3(kBlock), 0, st, out, in, scale, n); break;
-    default: return MP4X_E_UNSUPPORTED;
-  }
-  return (int)hipGetLastError();
+  return with_dtype(dtype, [&](auto dtc) {
+    constexpr int DT = decltype(dtc)::value;
+    if constexpr (is_float_dt<DT>()) {
+      hipLaunchKernelGGL(k_scale<DT>, dim3(grid_for(n, 4)), dim3(kBlock), 0, st, out, in, scale, n);
+      return (int)hipGetLastError();
+    } else {
+      return (int)MP4X_E_UNSUPPORTED;
+    }
+  });
 }
 
 // A/B hook for the kernel-variant sweep (tools/bench_kernels.py --variants).

@@ -93,10 +93,8 @@ __global__ __launch_bounds__(kBlock) void k_segment_reduce_vec(const int64_t* __
                                                                int64_t* __restrict__ out_keys,
                                                                u32x4* __restrict__ out_vals,
                                                                int32_t* __restrict__ out_count) {
-  using E = Elem<DT>;
-  using S = typename E::S;
-  using A = typename E::A;
-  constexpr int W = 16 / sizeof(S);
+  using A = typename Elem<DT>::A;
+  constexpr int W = 16 / sizeof(typename Elem<DT>::S);
   const int lane = threadIdx.x & 63;
   const int grp = lane / G, sub = lane % G, R = 64 / G;
   const int64_t nruns = *nruns_dev;
@@ -113,34 +111,17 @@ __global__ __launch_bounds__(kBlock) void k_segment_reduce_vec(const int64_t* __
       if (out_count) out_count[u] = (int32_t)(e - s);
     }
     for (int64_t v = sub; v < V; v += G) {
-      S x[W];
-      u32x4 t = vals[perm[s] * V + v];
-      __builtin_memcpy(x, &t, 16);
       A acc[W];
-#pragma unroll
-      for (int j = 0; j < W; ++j) acc[j] = E::load(x[j]);
+      unpack<DT>(vals[perm[s] * V + v], acc);
       int64_t j = (OP == MP4X_FIRST) ? e : s + 1;   // FIRST (K8 dedupe): the run's first row only
       for (; j + 1 < e; j += 2) {          // two rows in flight
-        u32x4 t0 = vals[perm[j] * V + v];
-        u32x4 t1 = vals[perm[j + 1] * V + v];
-        S y0[W], y1[W];
-        __builtin_memcpy(y0, &t0, 16);
-        __builtin_memcpy(y1, &t1, 16);
-#pragma unroll
-        for (int q = 0; q < W; ++q) acc[q] = combine<DT, OP>(combine<DT, OP>(acc[q], E::load(y0[q])), E::load(y1[q]));
+        const u32x4 t0 = vals[perm[j] * V + v];
+        const u32x4 t1 = vals[perm[j + 1] * V + v];
+        fold_in<DT, OP>(acc, t0);
+        fold_in<DT, OP>(acc, t1);
       }
-      if (j < e) {
-        u32x4 t0 = vals[perm[j] * V + v];
-        S y0[W];
-        __builtin_memcpy(y0, &t0, 16);
-#pragma unroll
-        for (int q = 0; q < W; ++q) acc[q] = combine<DT, OP>(acc[q], E::load(y0[q]));
-      }
-#pragma unroll
-      for (int q = 0; q < W; ++q) x[q] = E::store(acc[q]);
-      u32x4 o;
-      __builtin_memcpy(&o, x, 16);
-      out_vals[u * V + v] = o;
+      if (j < e) fold_in<DT, OP>(acc, vals[perm[j] * V + v]);
+      out_vals[u * V + v] = pack<DT, u32x4>(acc);
     }
   }
 }
@@ -149,41 +130,21 @@ template <int DT, int OP>
 static int launch_sr(const int64_t* sk, const int64_t* perm, const int64_t* starts, const int64_t* nr, int64_t n,
                      int64_t max_runs, const void* vals, int64_t dim, int64_t* ok, void* ov, int32_t* oc,
                      hipStream_t st) {
-  if constexpr (!op_valid<DT, OP>()) {
-    return MP4X_E_UNSUPPORTED;
-  } else {
-    using S = typename Elem<DT>::S;
-    const int64_t row_bytes = dim * (int64_t)sizeof(S);
-    if (vals && (row_bytes & 15) == 0 && ((((uintptr_t)vals | (uintptr_t)ov) & 15) == 0)) {
-      const int64_t V = row_bytes / 16;
-      int G = 1;
-      while (G < V && G < 64) G <<= 1;
-      int g = grid_for((max_runs * G + 63) / 64 * 64, 1);
-      hipLaunchKernelGGL((k_segment_reduce_vec<DT, OP>), dim3(g), dim3(kBlock), 0, st, sk, perm, starts, nr, n,
-                         (const u32x4*)vals, V, G, ok, (u32x4*)ov, oc);
-      return (int)hipGetLastError();
-    }
-    int g = grid_for(max_runs * 64, 1);
-    hipLaunchKernelGGL((k_segment_reduce<DT, OP>), dim3(g), dim3(kBlock), 0, st, sk, perm, starts, nr, n, vals, dim,
-                       ok, ov, oc);
+  using S = typename Elem<DT>::S;
+  const int64_t row_bytes = dim * (int64_t)sizeof(S);
+  if (vals && (row_bytes & 15) == 0 && ((((uintptr_t)vals | (uintptr_t)ov) & 15) == 0)) {
+    const int64_t V = row_bytes / 16;
+    int G = 1;
+    while (G < V && G < 64) G <<= 1;
+    int g = grid_for((max_runs * G + 63) / 64 * 64, 1);
+    hipLaunchKernelGGL((k_segment_reduce_vec<DT, OP>), dim3(g), dim3(kBlock), 0, st, sk, perm, starts, nr, n,
+                       (const u32x4*)vals, V, G, ok, (u32x4*)ov, oc);
     return (int)hipGetLastError();
   }
-}
-
-template <int DT>
-static int sr_dt(int op, const int64_t* sk, const int64_t* perm, const int64_t* starts, const int64_t* nr, int64_t n,
-                 int64_t mr, const void* vals, int64_t dim, int64_t* ok, void* ov, int32_t* oc, hipStream_t st) {
-  switch (op) {
-    case MP4X_SUM: return launch_sr<DT, MP4X_SUM>(sk, perm, starts, nr, n, mr, vals, dim, ok, ov, oc, st);
-    case MP4X_MAX: return launch_sr<DT, MP4X_MAX>(sk, perm, starts, nr, n, mr, vals, dim, ok, ov, oc, st);
-    case MP4X_MIN: return launch_sr<DT, MP4X_MIN>(sk, perm, starts, nr, n, mr, vals, dim, ok, ov, oc, st);
-    case MP4X_PROD: return launch_sr<DT, MP4X_PROD>(sk, perm, starts, nr, n, mr, vals, dim, ok, ov, oc, st);
-    case MP4X_BAND: return launch_sr<DT, MP4X_BAND>(sk, perm, starts, nr, n, mr, vals, dim, ok, ov, oc, st);
-    case MP4X_BOR: return launch_sr<DT, MP4X_BOR>(sk, perm, starts, nr, n, mr, vals, dim, ok, ov, oc, st);
-    case MP4X_BXOR: return launch_sr<DT, MP4X_BXOR>(sk, perm, starts, nr, n, mr, vals, dim, ok, ov, oc, st);
-    case MP4X_FIRST: return launch_sr<DT, MP4X_FIRST>(sk, perm, starts, nr, n, mr, vals, dim, ok, ov, oc, st);
-    default: return MP4X_E_UNSUPPORTED;
-  }
+  int g = grid_for(max_runs * 64, 1);
+  hipLaunchKernelGGL((k_segment_reduce<DT, OP>), dim3(g), dim3(kBlock), 0, st, sk, perm, starts, nr, n, vals, dim,
+                     ok, ov, oc);
+  return (int)hipGetLastError();
 }
 
 
@@ -424,18 +385,13 @@ extern "C" int mp4x_segment_reduce_rows(int dtype, int op, const int64_t* sk, co
                                         void* stream) {
   if (n <= 0 || max_runs <= 0) return 0;
   hipStream_t st = (hipStream_t)stream;
-  switch (dtype) {
-    case MP4X_F64: return sr_dt<MP4X_F64>(op, sk, perm, starts, nruns_dev, n, max_runs, vals, dim, out_keys, out_vals, out_count, st);
-    case MP4X_F32: return sr_dt<MP4X_F32>(op, sk, perm, starts, nruns_dev, n, max_runs, vals, dim, out_keys, out_vals, out_count, st);
-    case MP4X_I64: return sr_dt<MP4X_I64>(op, sk, perm, starts, nruns_dev, n, max_runs, vals, dim, out_keys, out_vals, out_count, st);
-    case MP4X_I32: return sr_dt<MP4X_I32>(op, sk, perm, starts, nruns_dev, n, max_runs, vals, dim, out_keys, out_vals, out_count, st);
-    case MP4X_BF16: return sr_dt<MP4X_BF16>(op, sk, perm, starts, nruns_dev, n, max_runs, vals, dim, out_keys, out_vals, out_count, st);
-    case MP4X_F16: return sr_dt<MP4X_F16>(op, sk, perm, starts, nruns_dev, n, max_runs, vals, dim, out_keys, out_vals, out_count, st);
-    case MP4X_I16: return sr_dt<MP4X_I16>(op, sk, perm, starts, nruns_dev, n, max_runs, vals, dim, out_keys, out_vals, out_count, st);
-    case MP4X_I8: return sr_dt<MP4X_I8>(op, sk, perm, starts, nruns_dev, n, max_runs, vals, dim, out_keys, out_vals, out_count, st);
-    case MP4X_U8: return sr_dt<MP4X_U8>(op, sk, perm, starts, nruns_dev, n, max_runs, vals, dim, out_keys, out_vals, out_count, st);
-    default: return MP4X_E_UNSUPPORTED;
-  }
+  return with_dtype(dtype, [&](auto dtc) {
+    constexpr int DT = decltype(dtc)::value;
+    return with_op_of<DT>(RowOpsFirst{}, op, MP4X_E_UNSUPPORTED, [&](auto opc) {
+      return launch_sr<DT, decltype(opc)::value>(sk, perm, starts, nruns_dev, n, max_runs, vals, dim, out_keys,
+                                                 out_vals, out_count, st);
+    });
+  });
 }
 
 static size_t pack_align(size_t x) { return (x + 255) & ~(size_t)255; }

@@ -165,10 +165,9 @@ __global__ __launch_bounds__(kBlock) void k_hash_reduce(const int32_t* __restric
                                                         const unsigned long long* __restrict__ m_dev,
                                                         const void* __restrict__ vals_, int64_t units, int G,
                                                         void* __restrict__ out_, int32_t* __restrict__ out_count) {
-  using E = Elem<DT>;
-  using S = typename E::S;
-  using A = typename E::A;
-  using U = typename std::conditional<VEC, u32x4, S>::type;
+  using S = typename Elem<DT>::S;
+  using A = typename Elem<DT>::A;
+  using U = typename std::conditional<VEC, u32x4, S>::type;   // a row's unit: 16 bytes, or one element
   constexpr int W = VEC ? 16 / (int)sizeof(S) : 1;
   __shared__ int32_t s_idx[kBlock / kMinG][kOrderMax];
   const U* vals = reinterpret_cast<const U*>(vals_);
@@ -206,45 +205,23 @@ __global__ __launch_bounds__(kBlock) void k_hash_reduce(const int32_t* __restric
     const bool listed = L <= kOrderMax;
     for (int64_t v = sub; v < units; v += G) {
       A acc[W];
-      auto load = [&](int32_t row, A* dst) {
-        U t = vals[(int64_t)row * units + v];
-        S x[W];
-        __builtin_memcpy(x, &t, sizeof(U));
-#pragma unroll
-        for (int q = 0; q < W; ++q) dst[q] = E::load(x[q]);
-      };
+      auto row = [&](int32_t i) { return vals[(int64_t)i * units + v]; };
       if (listed) {
-        load(buf[0], acc);
+        unpack<DT>(row(buf[0]), acc);
         int j = 1;
         for (; j + 1 < L; j += 2) {                      // two rows in flight
-          A y0[W], y1[W];
-          load(buf[j], y0);
-          load(buf[j + 1], y1);
-#pragma unroll
-          for (int q = 0; q < W; ++q) acc[q] = combine<DT, OP>(combine<DT, OP>(acc[q], y0[q]), y1[q]);
+          const U t0 = row(buf[j]);
+          const U t1 = row(buf[j + 1]);
+          fold_in<DT, OP>(acc, t0);
+          fold_in<DT, OP>(acc, t1);
         }
-        if (j < L) {
-          A y0[W];
-          load(buf[j], y0);
-#pragma unroll
-          for (int q = 0; q < W; ++q) acc[q] = combine<DT, OP>(acc[q], y0[q]);
-        }
+        if (j < L) fold_in<DT, OP>(acc, row(buf[j]));
       } else {
         int32_t i = rhead[u];
-        load(i, acc);
-        for (i = next[i]; i >= 0; i = next[i]) {
-          A y0[W];
-          load(i, y0);
-#pragma unroll
-          for (int q = 0; q < W; ++q) acc[q] = combine<DT, OP>(acc[q], y0[q]);
-        }
+        unpack<DT>(row(i), acc);
+        for (i = next[i]; i >= 0; i = next[i]) fold_in<DT, OP>(acc, row(i));
       }
-      S x[W];
-#pragma unroll
-      for (int q = 0; q < W; ++q) x[q] = E::store(acc[q]);
-      U o;
-      __builtin_memcpy(&o, x, sizeof(U));
-      out[u * units + v] = o;
+      out[u * units + v] = pack<DT, U>(acc);
     }
   }
 }
@@ -393,39 +370,31 @@ Layout layout(int64_t n) {
 template <int DT, int OP>
 int launch_reduce(const int32_t* rhead, const int32_t* next, const unsigned long long* m_dev, int64_t n,
                   const void* vals, int64_t dim, void* out, int32_t* out_count, hipStream_t st) {
-  if constexpr (!op_valid<DT, OP>()) {
-    return MP4X_E_UNSUPPORTED;
-  } else {
-    using S = typename Elem<DT>::S;
-    const int64_t row_bytes = dim * (int64_t)sizeof(S);
-    const bool vec = (row_bytes & 15) == 0 && ((((uintptr_t)vals | (uintptr_t)out) & 15) == 0);
-    const int64_t units = vec ? row_bytes / 16 : dim;
-    int G = kMinG;
-    while (G < units && G < 64) G <<= 1;
-    const int g = grid_for((n * G + 63) / 64 * 64, 1);
-    if (vec)
-      hipLaunchKernelGGL((k_hash_reduce<DT, OP, true>), dim3(g), dim3(kBlock), 0, st, rhead, next, m_dev, vals, units,
-                         G, out, out_count);
-    else
-      hipLaunchKernelGGL((k_hash_reduce<DT, OP, false>), dim3(g), dim3(kBlock), 0, st, rhead, next, m_dev, vals, units,
-                         G, out, out_count);
-    return (int)hipGetLastError();
-  }
+  using S = typename Elem<DT>::S;
+  const int64_t row_bytes = dim * (int64_t)sizeof(S);
+  const bool vec = (row_bytes & 15) == 0 && ((((uintptr_t)vals | (uintptr_t)out) & 15) == 0);
+  const int64_t units = vec ? row_bytes / 16 : dim;
+  int G = kMinG;
+  while (G < units && G < 64) G <<= 1;
+  const int g = grid_for((n * G + 63) / 64 * 64, 1);
+  if (vec)
+    hipLaunchKernelGGL((k_hash_reduce<DT, OP, true>), dim3(g), dim3(kBlock), 0, st, rhead, next, m_dev, vals, units,
+                       G, out, out_count);
+  else
+    hipLaunchKernelGGL((k_hash_reduce<DT, OP, false>), dim3(g), dim3(kBlock), 0, st, rhead, next, m_dev, vals, units,
+                       G, out, out_count);
+  return (int)hipGetLastError();
 }
 
-template <int DT>
-int reduce_dt(int op, const int32_t* rhead, const int32_t* next, const unsigned long long* m_dev, int64_t n,
-              const void* vals, int64_t dim, void* out, int32_t* oc, hipStream_t st) {
-  switch (op) {
-    case MP4X_SUM: return launch_reduce<DT, MP4X_SUM>(rhead, next, m_dev, n, vals, dim, out, oc, st);
-    case MP4X_MAX: return launch_reduce<DT, MP4X_MAX>(rhead, next, m_dev, n, vals, dim, out, oc, st);
-    case MP4X_MIN: return launch_reduce<DT, MP4X_MIN>(rhead, next, m_dev, n, vals, dim, out, oc, st);
-    case MP4X_PROD: return launch_reduce<DT, MP4X_PROD>(rhead, next, m_dev, n, vals, dim, out, oc, st);
-    case MP4X_BAND: return launch_reduce<DT, MP4X_BAND>(rhead, next, m_dev, n, vals, dim, out, oc, st);
-    case MP4X_BOR: return launch_reduce<DT, MP4X_BOR>(rhead, next, m_dev, n, vals, dim, out, oc, st);
-    case MP4X_BXOR: return launch_reduce<DT, MP4X_BXOR>(rhead, next, m_dev, n, vals, dim, out, oc, st);
-    default: return MP4X_E_UNSUPPORTED;
-  }
+// The reduce launch of both entry points (hash and dense), for a runtime (dtype, op).
+int reduce_runs(int dtype, int op, const int32_t* rhead, const int32_t* next, const unsigned long long* m_dev,
+                int64_t n, const void* vals, int64_t dim, void* out, int32_t* out_count, hipStream_t st) {
+  return with_dtype(dtype, [&](auto dtc) {
+    constexpr int DT = decltype(dtc)::value;
+    return with_op_of<DT>(RowOps{}, op, MP4X_E_UNSUPPORTED, [&](auto opc) {
+      return launch_reduce<DT, decltype(opc)::value>(rhead, next, m_dev, n, vals, dim, out, out_count, st);
+    });
+  });
 }
 }  // namespace
 
@@ -465,15 +434,7 @@ extern "C" size_t mp4x_hash_rbk_scratch_bytes(int64_t n) { return layout(n < 0 ?
 
 // Does the hash path serve (dtype, op)?  1 / 0.  (Every reduction of the segmented reduce except
 // the FIRST rule, which needs the rank order of arbitrarily long runs.)
-extern "C" int mp4x_hash_rbk_supported(int dtype, int op) {
-  if (op == MP4X_FIRST) return 0;
-  const bool isint = dtype == MP4X_I64 || dtype == MP4X_I32 || dtype == MP4X_I16 || dtype == MP4X_I8 ||
-                     dtype == MP4X_U8;
-  const bool isflt = dtype == MP4X_F64 || dtype == MP4X_F32 || dtype == MP4X_BF16 || dtype == MP4X_F16;
-  if (!isint && !isflt) return 0;
-  if (op == MP4X_SUM || op == MP4X_MAX || op == MP4X_MIN || op == MP4X_PROD) return 1;
-  return isint && (op == MP4X_BAND || op == MP4X_BOR || op == MP4X_BXOR) ? 1 : 0;
-}
+extern "C" int mp4x_hash_rbk_supported(int dtype, int op) { return pair_supported(RowOps{}, dtype, op) == 0; }
 
 // keys[n], vals[n][dim] -> out_keys[m] (table order), out_vals[m][dim], out_count[m] (optional);
 // m_flag[0] = m, written on the device (stream-ordered; m_flag[1] is zeroed).  out_* must hold
@@ -502,18 +463,7 @@ extern "C" int mp4x_hash_reduce_by_key(int dtype, int op, const int64_t* keys, i
                      (const SideRun*)side);
   if (int e = (int)hipGetLastError()) return e;
   const unsigned long long* m_dev = counter;
-  switch (dtype) {
-    case MP4X_F64: return reduce_dt<MP4X_F64>(op, rhead, next, m_dev, n, vals, dim, out_vals, out_count, st);
-    case MP4X_F32: return reduce_dt<MP4X_F32>(op, rhead, next, m_dev, n, vals, dim, out_vals, out_count, st);
-    case MP4X_I64: return reduce_dt<MP4X_I64>(op, rhead, next, m_dev, n, vals, dim, out_vals, out_count, st);
-    case MP4X_I32: return reduce_dt<MP4X_I32>(op, rhead, next, m_dev, n, vals, dim, out_vals, out_count, st);
-    case MP4X_BF16: return reduce_dt<MP4X_BF16>(op, rhead, next, m_dev, n, vals, dim, out_vals, out_count, st);
-    case MP4X_F16: return reduce_dt<MP4X_F16>(op, rhead, next, m_dev, n, vals, dim, out_vals, out_count, st);
-    case MP4X_I16: return reduce_dt<MP4X_I16>(op, rhead, next, m_dev, n, vals, dim, out_vals, out_count, st);
-    case MP4X_I8: return reduce_dt<MP4X_I8>(op, rhead, next, m_dev, n, vals, dim, out_vals, out_count, st);
-    case MP4X_U8: return reduce_dt<MP4X_U8>(op, rhead, next, m_dev, n, vals, dim, out_vals, out_count, st);
-    default: return MP4X_E_UNSUPPORTED;
-  }
+  return reduce_runs(dtype, op, rhead, next, m_dev, n, vals, dim, out_vals, out_count, st);
 }
 
 extern "C" size_t mp4x_dense_rbk_scratch_bytes(int64_t n, int64_t T) {
@@ -561,16 +511,5 @@ extern "C" int mp4x_dense_reduce_by_key(int dtype, int op, const int64_t* keys, 
                        (const int32_t*)next, m_dev, out_count);
     return (int)hipGetLastError();
   }
-  switch (dtype) {
-    case MP4X_F64: return reduce_dt<MP4X_F64>(op, rhead, next, m_dev, n, vals, dim, out_vals, out_count, st);
-    case MP4X_F32: return reduce_dt<MP4X_F32>(op, rhead, next, m_dev, n, vals, dim, out_vals, out_count, st);
-    case MP4X_I64: return reduce_dt<MP4X_I64>(op, rhead, next, m_dev, n, vals, dim, out_vals, out_count, st);
-    case MP4X_I32: return reduce_dt<MP4X_I32>(op, rhead, next, m_dev, n, vals, dim, out_vals, out_count, st);
-    case MP4X_BF16: return reduce_dt<MP4X_BF16>(op, rhead, next, m_dev, n, vals, dim, out_vals, out_count, st);
-    case MP4X_F16: return reduce_dt<MP4X_F16>(op, rhead, next, m_dev, n, vals, dim, out_vals, out_count, st);
-    case MP4X_I16: return reduce_dt<MP4X_I16>(op, rhead, next, m_dev, n, vals, dim, out_vals, out_count, st);
-    case MP4X_I8: return reduce_dt<MP4X_I8>(op, rhead, next, m_dev, n, vals, dim, out_vals, out_count, st);
-    case MP4X_U8: return reduce_dt<MP4X_U8>(op, rhead, next, m_dev, n, vals, dim, out_vals, out_count, st);
-    default: return MP4X_E_UNSUPPORTED;
-  }
+  return reduce_runs(dtype, op, rhead, next, m_dev, n, vals, dim, out_vals, out_count, st);
 }

@@ -305,12 +305,7 @@ extern "C" int mp4x_ipc_allreduce(int algo, int dtype, int op, void* const* data
 }
 
 // Does the IPC allreduce have a kernel for (dtype, op)?  1 / 0.
-extern "C" int mp4x_ipc_op_supported(int dtype, int op) {
-  return with_dtype(dtype, [&](auto dtc) {
-    constexpr int DT = decltype(dtc)::value;
-    return with_op<DT>(op, [&](auto) { return 1; }) == 1 ? 1 : 0;
-  }) == 1 ? 1 : 0;
-}
+extern "C" int mp4x_ipc_op_supported(int dtype, int op) { return op_supported(dtype, op) == 0; }
 
 // Blocks per CU the occupancy API admits for the kernel a call of (algo, dtype, op, p) launches
 // (the shared-GPU co-residency budget, mp4x/parallel/occupancy.py).

@@ -57,7 +57,6 @@
 //    one GPU).
 #pragma once
 #include <hip/hip_runtime.h>
-#include <type_traits>
 
 #include "../kernels/common.hpp"
 
@@ -244,39 +243,6 @@ __device__ __forceinline__ bool block_barrier(const IpcPtrs& P, int which, int r
   return s_fail == 0;
 }
 
-// Combine of NR 16-byte vectors (rank order: r[0] first, deterministic), then the optional
-// fused scale (float dtypes, a wave-uniform branch; 1.0 = plain reduction).
-template <int DT, int OP, int NR>
-__device__ __forceinline__ u32x4 fold_vec(const u32x4 (&r)[NR], float scale) {
-  using E = Elem<DT>;
-  using S = typename E::S;
-  using A = typename E::A;
-  constexpr int W = 16 / sizeof(S);
-  S s[W];
-  __builtin_memcpy(s, &r[0], 16);
-  A acc[W];
-#pragma unroll
-  for (int j = 0; j < W; ++j) acc[j] = E::load(s[j]);
-#pragma unroll
-  for (int k = 1; k < NR; ++k) {
-    S x[W];
-    __builtin_memcpy(x, &r[k], 16);
-#pragma unroll
-    for (int j = 0; j < W; ++j) acc[j] = combine<DT, OP>(acc[j], E::load(x[j]));
-  }
-  if constexpr (is_float_dt<DT>()) {
-    if (scale != 1.0f) {
-#pragma unroll
-      for (int j = 0; j < W; ++j) acc[j] = acc[j] * (A)scale;
-    }
-  }
-#pragma unroll
-  for (int j = 0; j < W; ++j) s[j] = E::store(acc[j]);
-  u32x4 o;
-  __builtin_memcpy(&o, s, 16);
-  return o;
-}
-
 // OP = kOpRt: the combine chosen by the kernel argument `op` (validated on the host against
 // op_valid; one scalar branch per vector after the loads are in flight).
 template <int DT, int OP, int NR>
@@ -320,47 +286,15 @@ __device__ __forceinline__ uint32_t resolve_epoch(uint32_t epoch, const uint32_t
 }
 
 // ---------------------------------------------------------------- host-side dispatch
-template <int V> using IntC = std::integral_constant<int, V>;
-
 // (dtype, op) pairs with kernels of their own (compile-time op): the DP gradient / statistic path.
 template <int DT> constexpr bool hot_sum() {
   return DT == MP4X_F64 || DT == MP4X_F32 || DT == MP4X_I64 || DT == MP4X_I32 || DT == MP4X_BF16 || DT == MP4X_F16;
 }
 template <int DT> constexpr bool hot_minmax() { return DT == MP4X_F32 || DT == MP4X_BF16 || DT == MP4X_F16; }
 
-// Every reduction of the reference's operator table for DT (MP4X_FIRST is a sparse-merge rule,
-// not a collective operator).
+// Every reduction of the reference's operator table for DT.
 template <int DT> inline bool rt_op_ok(int op) {
-  switch (op) {
-    case MP4X_SUM: return op_valid<DT, MP4X_SUM>();
-    case MP4X_MAX: return op_valid<DT, MP4X_MAX>();
-    case MP4X_MIN: return op_valid<DT, MP4X_MIN>();
-    case MP4X_PROD: return op_valid<DT, MP4X_PROD>();
-    case MP4X_BAND: return op_valid<DT, MP4X_BAND>();
-    case MP4X_BOR: return op_valid<DT, MP4X_BOR>();
-    case MP4X_BXOR: return op_valid<DT, MP4X_BXOR>();
-    case MP4X_FMAXLOC: return op_valid<DT, MP4X_FMAXLOC>();
-    case MP4X_FMINLOC: return op_valid<DT, MP4X_FMINLOC>();
-    case MP4X_IMAXLOC: return op_valid<DT, MP4X_IMAXLOC>();
-    case MP4X_IMINLOC: return op_valid<DT, MP4X_IMINLOC>();
-    default: return false;
-  }
-}
-
-// f(IntC<DT>{}) for a runtime dtype code.
-template <typename F> inline int with_dtype(int dtype, F&& f) {
-  switch (dtype) {
-    case MP4X_F64: return f(IntC<MP4X_F64>{});
-    case MP4X_F32: return f(IntC<MP4X_F32>{});
-    case MP4X_I64: return f(IntC<MP4X_I64>{});
-    case MP4X_I32: return f(IntC<MP4X_I32>{});
-    case MP4X_I16: return f(IntC<MP4X_I16>{});
-    case MP4X_I8: return f(IntC<MP4X_I8>{});
-    case MP4X_BF16: return f(IntC<MP4X_BF16>{});
-    case MP4X_F16: return f(IntC<MP4X_F16>{});
-    case MP4X_U8: return f(IntC<MP4X_U8>{});
-    default: return MP4X_E_UNSUPPORTED;
-  }
+  return with_op_of<DT>(TableOps{}, op, MP4X_E_UNSUPPORTED, [](auto) { return 0; }) == 0;
 }
 
 // f(IntC<OP>{}) with the kernel op of (DT, op): a hot pair's own op, else kOpRt.
@@ -378,26 +312,10 @@ template <int DT, typename F> inline int with_op(int op, F&& f) {
 
 // 0 when the IPC kernels reduce `op` over `dtype` (a hot pair or the runtime-op kernel), else
 // MP4X_E_UNSUPPORTED — the refusal with_dtype / with_op would make at launch time.
-inline int op_supported(int dtype, int op) {
-  return with_dtype(dtype, [&](auto dtc) {
-    constexpr int DT = decltype(dtc)::value;
-    return with_op<DT>(op, [](auto) { return 0; });
-  });
-}
+inline int op_supported(int dtype, int op) { return pair_supported(TableOps{}, dtype, op); }
 
 // f(IntC<NR>{}) for a rank count 2..8.
-template <typename F> inline int with_nr(int p, F&& f) {
-  switch (p) {
-    case 2: return f(IntC<2>{});
-    case 3: return f(IntC<3>{});
-    case 4: return f(IntC<4>{});
-    case 5: return f(IntC<5>{});
-    case 6: return f(IntC<6>{});
-    case 7: return f(IntC<7>{});
-    case 8: return f(IntC<8>{});
-    default: return MP4X_E_BADARG;
-  }
-}
+template <typename F> inline int with_nr(int p, F&& f) { return with_count<2>(p, static_cast<F&&>(f)); }
 
 // Blocks per CU the occupancy API admits for `kern` at kIpcThreads threads (min-folded into *m).
 template <typename K> inline void occ_min(K kern, int* m) {
@@ -425,10 +343,6 @@ inline int ipc_blocks(int blocks, int64_t nvec) {
     blocks = (int)(b < 1 ? 1 : (b > kIpcMaxBlocks ? kIpcMaxBlocks : b));
   }
   return blocks > kIpcMaxBlocks ? kIpcMaxBlocks : blocks;
-}
-
-inline bool float_dtype(int dtype) {
-  return dtype == MP4X_F32 || dtype == MP4X_F64 || dtype == MP4X_BF16 || dtype == MP4X_F16;
 }
 
 }  // namespace mp4x

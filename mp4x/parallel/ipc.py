@@ -185,8 +185,9 @@ def ipc_op_ok(dtype, op) -> bool:
     """Does the IPC tier reduce ``op`` over ``dtype``?  Every operator of the reference's table
     (Operators.java:29-353) for every primitive dtype, plus 16-bit floats and uint8: SUM / MAX /
     MIN / PROD everywhere, BITS_AND / OR / XOR on integers, FLOAT_*_LOC on the packed f64 words,
-    INT_*_LOC on the packed i64 words (csrc/runtime/ipc_common.hpp rt_op_ok).  Custom operators
-    (possibly non-commutative host callables) never run here."""
+    INT_*_LOC on the packed i64 words — the native table is ``op_valid`` over ``TableOps`` in
+    csrc/kernels/common.hpp (``mp4x_ipc_op_supported``; tests/test_dispatch_table_cpu.py holds the
+    two in agreement).  Custom operators (possibly non-commutative host callables) never run here."""
     if getattr(op, "is_custom", False) or dtype not in SUPPORTED_DTYPES:
         return False
     c = op.code

@@ -124,6 +124,118 @@ def test_reduce_unaligned_views():
     torch.testing.assert_close(out, xs[0] + xs[1] + xs[2])
 
 
+@pytest.mark.parametrize("cap", [0, 1])
+@pytest.mark.parametrize("variant", [0, 1, 2, 3])
+@pytest.mark.parametrize("nin", [1, 3, 8])
+def test_reduce_k1_variants_bit_exact(nin, variant, cap):
+    """Every MP4X_K1_VARIANT (f32), with one tile per block (cap 0) and with the grid-stride loop
+    forced (cap 1).  n = 9247: 2311 vectors = two full 4-vector tiles, a partial tile, 7 whole
+    vectors past it, and a 3-element tail.  The kernels combine in input order, so f32 torch in the
+    same order is equal bit for bit."""
+    K = _native()
+    from mp4x.ops import native
+    lib = native.hip()
+    n = 9247
+    g = torch.Generator(device=DEV).manual_seed(nin)
+    xs = [torch.randn(n, device=DEV, generator=g) for _ in range(nin)]
+    ref = xs[0].clone()
+    for x in xs[1:]:
+        ref = ref + x
+    out = torch.empty_like(xs[0])
+    try:
+        lib.mp4x_set_k1_variant(variant)
+        lib.mp4x_set_k1_grid(cap)
+        K.reduce_(out, xs, int(OpCode.SUM))
+        torch.cuda.synchronize()
+    finally:
+        lib.mp4x_set_k1_variant(2)      # the default
+        lib.mp4x_set_k1_grid(-1)        # negative: re-read the environment, back to the default
+    assert torch.equal(out, ref)
+
+
+_RBK_DTYPES = [torch.float64, torch.float32, torch.int64, torch.int32, torch.int16, torch.int8, torch.bfloat16,
+               torch.float16, torch.uint8]
+_RBK_FIRST = 11
+_RBK_CASES = [(dt, code) for dt in _RBK_DTYPES
+              for code in [OpCode.SUM, OpCode.MAX, OpCode.MIN, OpCode.PROD]
+              + ([] if dt.is_floating_point else [OpCode.BAND, OpCode.BOR, OpCode.BXOR]) + [_RBK_FIRST]]
+
+
+def _rbk_combine(a, b, code):
+    """combine(a, b) of csrc/kernels/common.hpp, on CPU tensors of the accumulator type."""
+    if code == OpCode.SUM:
+        return a + b
+    if code == OpCode.PROD:
+        return a * b
+    if code == OpCode.MAX:
+        return torch.where(a >= b, a, b)
+    if code == OpCode.MIN:
+        return torch.where(a <= b, a, b)
+    if code == OpCode.BAND:
+        return a & b
+    if code == OpCode.BOR:
+        return a | b
+    if code == OpCode.BXOR:
+        return a ^ b
+    return a                                               # FIRST
+
+
+def _rbk_ref(keys, vals, code):
+    """CPU loop: every key's rows combined in input order in the accumulator type (f32 for the
+    16-bit floats, rounded once; integers wrap) -> (keys ascending, rows, counts)."""
+    acc_t = torch.float32 if vals.dtype in (torch.bfloat16, torch.float16) else vals.dtype
+    v = vals.to(acc_t)
+    acc, cnt = {}, {}
+    for i, k in enumerate(keys.tolist()):
+        acc[k] = _rbk_combine(acc[k], v[i], code) if k in acc else v[i].clone()
+        cnt[k] = cnt.get(k, 0) + 1
+    uk = sorted(acc)
+    return (torch.tensor(uk, dtype=torch.int64), torch.stack([acc[k] for k in uk]).to(vals.dtype),
+            torch.tensor([cnt[k] for k in uk], dtype=torch.int32))
+
+
+@pytest.mark.parametrize("dtype,code", _RBK_CASES, ids=lambda v: str(v).replace("torch.", ""))
+def test_reduce_by_key_over_the_table(dtype, code):
+    """Every (dtype, row op) pair on the sort path, the hash path and the dense path, with rows of
+    exactly 16 bytes (the vector kernels) and of 3 elements (the scalar kernels), against a CPU loop
+    in input order: equal bit for bit.  FIRST is served by the sort path only."""
+    K = _native()
+    n = 300
+    g = torch.Generator().manual_seed(17)
+    keys = torch.randint(0, 41, (n,), generator=g, dtype=torch.int64)
+    # longer runs combine in list order on the hash path (kOrderMax, csrc/kernels/sparse_hash.hip)
+    assert int(torch.bincount(keys).max()) <= 64
+    for dim in (16 // torch.empty(0, dtype=dtype).element_size(), 3):
+        if dtype.is_floating_point:
+            vals = torch.randn(n, dim, generator=g, dtype=torch.float32)
+            if code == OpCode.PROD:
+                vals = vals.clamp(-1.5, 1.5)
+            vals = vals.to(dtype)
+        elif dtype == torch.uint8:
+            vals = torch.randint(0, 100, (n, dim), generator=g, dtype=torch.int64).to(dtype)
+        else:
+            vals = torch.randint(-50, 50, (n, dim), generator=g, dtype=torch.int64).to(dtype)
+        ref_k, ref_v, ref_c = _rbk_ref(keys, vals, code)
+        dk, dv = keys.to(DEV), vals.to(DEV)
+
+        def same(got, path):
+            uk, uv, cnt = got
+            assert torch.equal(uk.cpu(), ref_k), (path, dim)
+            assert torch.equal(cnt.cpu(), ref_c), (path, dim)
+            # bit for bit: compare the storage, so -0.0 != 0.0 and NaN == NaN
+            assert torch.equal(uv.cpu().view(torch.uint8), ref_v.view(torch.uint8)), (path, dim)
+
+        same(K.reduce_by_key(dk, dv, int(code)), "sort")
+        if code == _RBK_FIRST:
+            continue
+        hk, hv, hc = K.hash_reduce_by_key(dk, dv, int(code))
+        order = torch.argsort(hk)
+        same((hk[order], hv[order], hc[order]), "hash")
+        dense = K.dense_reduce_by_key(dk, dv, int(code), 0, 1, 64)
+        assert dense is not None
+        same(dense, "dense")
+
+
 @pytest.mark.parametrize("dtype", [torch.float32, torch.float64, torch.bfloat16, torch.float16])
 @pytest.mark.parametrize("off", [0, 1])
 def test_scale(dtype, off):
