@@ -58,6 +58,10 @@ __device__ __forceinline__ float f16_to_f32(uint16_t h) {
   return (float)x;
 }
 __device__ __forceinline__ uint16_t f32_to_f16(float f) {
+  // The f32 value is pinned in a register first.  Left to itself the compiler fuses a product and
+  // this conversion into v_fma_mixlo_f16 a, b, +0, and (-0) + (+0) = +0 loses the sign of a zero
+  // product (f16 PROD and scale returned +0 for -0).
+  asm("" : "+v"(f));
   _Float16 x = (_Float16)f;
   uint16_t h;
   __builtin_memcpy(&h, &x, 2);

@@ -73,8 +73,15 @@ __device__ __forceinline__ void store4(void* p, int64_t e, int64_t n, const floa
 
 __device__ __forceinline__ uint32_t pack_fp8(const float (&x)[4], float inv) {
   float a[4];
+  // the clamp by comparisons, not fminf / fmaxf: those return the other operand for a NaN (a NaN
+  // input would encode as -448 and decode to -amax); a NaN fails both comparisons, passes through
+  // and encodes to the e4m3 NaN
 #pragma unroll
-  for (int j = 0; j < 4; ++j) a[j] = fminf(fmaxf(x[j] * inv, -kFp8Max), kFp8Max);
+  for (int j = 0; j < 4; ++j) {
+    const float v = x[j] * inv;
+    const float c = v > kFp8Max ? kFp8Max : v;
+    a[j] = c < -kFp8Max ? -kFp8Max : c;
+  }
   int w = __builtin_amdgcn_cvt_pk_fp8_f32(a[0], a[1], 0, false);
   w = __builtin_amdgcn_cvt_pk_fp8_f32(a[2], a[3], w, true);
   return (uint32_t)w;

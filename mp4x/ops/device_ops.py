@@ -111,33 +111,72 @@ def gather_rows(inp: torch.Tensor, idx: torch.Tensor, out: Optional[torch.Tensor
 
 
 # ------------------------------------------------------------------ fp8 codec (K6)
+# The buffer contract of the codec is WHOLE BLOCKS: the kernels move one dword per lane for every
+# lane of the last block, so a code buffer for n elements is nblk * 256 bytes (nblk = ceil(n / 256)),
+# and the quantiser writes the pad past n as zero codes.  The re-quantising dequant-reduce folds
+# the pad lanes into the last block's amax, so its inputs must carry that zero pad.
+def _room(t: torch.Tensor) -> int:
+    """Bytes from t's first element to the end of the allocation it is a view of."""
+    return t.untyped_storage().nbytes() - t.storage_offset() * t.element_size()
+
+
 def quant_fp8(x: torch.Tensor, q: Optional[torch.Tensor] = None, scales: Optional[torch.Tensor] = None,
               stream=None):
-    """Block-scaled e4m3 quantisation (256 elements / scale). Returns (q uint8[n], scales f32[nblk])."""
-    _dev_check(x)
+    """Block-scaled e4m3 quantisation (256 elements / scale). Returns (q uint8[n], scales f32[nblk]).
+
+    The kernel writes whole blocks: ``nblk * 256`` bytes, the pad past ``n`` as zero codes.  A
+    caller's ``q`` must hold that many (it is returned as given); without one the codes are
+    allocated as whole blocks and the first ``n`` bytes returned as a view of them, so the result
+    can be passed on to :func:`dequant_reduce_fp8` as it is.
+
+    A NaN element encodes to NaN and is ignored in its block's amax; a block with an infinity gets
+    an infinite scale and decodes to non-finite values throughout."""
+    _dev_check(x, q, scales)
     n = x.numel()
     if n % 4:
         raise ValueError("quant_fp8: n must be a multiple of 4")
     nblk = (n + QBLOCK - 1) // QBLOCK
-    if q is None:
-        q = torch.empty(n, dtype=torch.uint8, device=x.device)
+    own = q is None
+    if own:
+        q = torch.empty(nblk * QBLOCK, dtype=torch.uint8, device=x.device)
     if scales is None:
         scales = torch.empty(nblk, dtype=torch.float32, device=x.device)
-    if q.numel() < n or scales.numel() < nblk:
-        raise ValueError("quant_fp8: output too small")
+    if q.dtype != torch.uint8 or scales.dtype != torch.float32:
+        raise ValueError("quant_fp8: q must be uint8 and scales float32")
+    if q.numel() < nblk * QBLOCK or scales.numel() < nblk:
+        raise ValueError(f"quant_fp8: q needs whole blocks ({nblk * QBLOCK} bytes for n = {n}) and scales {nblk}")
     check(native.hip().mp4x_quant_fp8(int(dtype_of_torch(x.dtype)), x.data_ptr(), n, q.data_ptr(), scales.data_ptr(),
                                       stream_ptr(stream)), "mp4x_quant_fp8")
-    return q, scales
+    return (q[:n] if own else q), scales
 
 
 def dequant_reduce_fp8(out: Optional[torch.Tensor], qs: Sequence[torch.Tensor], ss: Sequence[torch.Tensor], n: int,
                        accumulate: bool = False, q_out: Optional[torch.Tensor] = None,
                        s_out: Optional[torch.Tensor] = None, out_dtype=None, stream=None):
+    """out[:n] (f32 / bf16 / f16) = [out +] sum_k dequant(qs[k], ss[k]), as the f32 chain
+    ``acc = fma(code_k, scale_k, acc)`` in input order, stored with one rounding; with ``q_out`` /
+    ``s_out`` the f32 accumulators (not the rounded ``out``) are re-quantised in the same pass.
+    ``out`` may be None when only the re-quantised result is wanted.
+
+    More than 8 inputs run as a chain of launches of up to 8.  The partial sums travel in f32 (in
+    an f32 ``out``, or in a temporary when ``out`` is None), so the result is the one chain over
+    all inputs, exactly.  A bf16 / f16 ``out`` carries them itself and so rounds once per launch of
+    8; the re-quantised result then starts each later launch from that rounded value.
+
+    Buffers are whole blocks (see :func:`quant_fp8`): ``q_out`` holds ``nblk * 256`` bytes, and
+    with ``q_out`` every input must be backed by ``nblk * 256`` bytes whose pad past ``n`` is zero
+    codes, as the quantiser writes them — the tensor itself or the allocation it is a view of (the
+    ``n``-byte view :func:`quant_fp8` returns qualifies)."""
     nblk = (n + QBLOCK - 1) // QBLOCK
+    if not qs or len(qs) != len(ss):
+        raise ValueError("dequant_reduce_fp8: one scale tensor per code tensor")
     for q, s in zip(qs, ss):
         _dev_check(q, s)
         if q.numel() < n or s.numel() < nblk:
             raise ValueError("dequant_reduce_fp8: input too small")
+        if q_out is not None and _room(q) < nblk * QBLOCK:
+            raise ValueError(f"dequant_reduce_fp8: with q_out every input needs whole blocks "
+                             f"({nblk * QBLOCK} bytes for n = {n})")
     if out is not None:
         _dev_check(out)
         if out.numel() < n:
@@ -145,8 +184,20 @@ def dequant_reduce_fp8(out: Optional[torch.Tensor], qs: Sequence[torch.Tensor], 
         dt = dtype_of_torch(out.dtype)
     else:
         dt = dtype_of_torch(out_dtype or torch.float32)
-    if q_out is not None and (q_out.numel() < n or s_out is None or s_out.numel() < nblk):
-        raise ValueError("dequant_reduce_fp8: requant outputs too small")
+    if q_out is not None:
+        _dev_check(q_out, s_out)
+        if q_out.numel() < nblk * QBLOCK or s_out is None or s_out.numel() < nblk:
+            raise ValueError(f"dequant_reduce_fp8: q_out needs whole blocks ({nblk * QBLOCK} bytes for n = {n}) "
+                             f"and s_out {nblk}")
+    if out is None and len(qs) > 8:
+        # the kernel keeps its partial sums in `out`: without one, chain through an f32 temporary
+        # (every launch would otherwise start from zero and q_out hold the last launch's sum only)
+        if n <= 0:
+            return None
+        out_k = torch.empty(n, dtype=torch.float32, device=qs[0].device)
+        dt = dtype_of_torch(torch.float32)
+    else:
+        out_k = out
     lib = native.hip()
     done = 0
     first = True
@@ -155,7 +206,7 @@ def dequant_reduce_fp8(out: Optional[torch.Tensor], qs: Sequence[torch.Tensor], 
         qp, k1 = ptr_array([t.data_ptr() for t in qs[done:done + k]])
         sp, k2 = ptr_array([t.data_ptr() for t in ss[done:done + k]])
         last = done + k == len(qs)
-        check(lib.mp4x_dequant_reduce_fp8(int(dt), out.data_ptr() if out is not None else None, qp, sp, k, n,
+        check(lib.mp4x_dequant_reduce_fp8(int(dt), out_k.data_ptr() if out_k is not None else None, qp, sp, k, n,
                                           int(accumulate or not first),
                                           q_out.data_ptr() if (q_out is not None and last) else None,
                                           s_out.data_ptr() if (s_out is not None and last) else None,
