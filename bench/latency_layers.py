@@ -41,9 +41,9 @@ def worker(port, q, nbytes, iters):
 
     def raw():
         inst.epoch = (inst.epoch + 1) & 0x3FFFFFFF or 1
-        lib.mp4x_ipc_allreduce_ex(ipcm.ONESHOT, dt, int(fop.code), inst._pp_data[0], inst._pp_sig[0], inst.rank,
-                                  inst.p, nbytes, x.data_ptr(), x.data_ptr(), inst.epoch, 8 if inst.shared_gpu else 0,
-                                  None, 1.0, st)
+        lib.mp4x_ipc_allreduce(ipcm.ONESHOT, dt, int(fop.code), inst._pp_data[0], inst._pp_sig[0], inst.rank,
+                               inst.p, nbytes, x.data_ptr(), x.data_ptr(), inst.epoch, 8 if inst.shared_gpu else 0,
+                               None, 1.0, st, 0, 0)
     fast_memo = comm._fast_ar
 
     def api_full():            # the public call with the latency fast path disarmed

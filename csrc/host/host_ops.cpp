@@ -36,7 +36,7 @@
 #include <time.h>
 #include <unistd.h>
 
-#include "mp4x/ops.h"
+#include "mp4x/host.h"
 
 namespace {
 
@@ -451,11 +451,6 @@ int mp4x_host_reduce(int dtype, int op, void* out, const void* const* ins, int n
   return host_reduce(dtype, op, out, ins, nin, n, nthreads);
 }
 
-int mp4x_host_threads(void) { return (int)std::thread::hardware_concurrency(); }
-
-int64_t mp4x_shm_header_bytes(void) { return 4096; }
-
-// rank 0 initialises the header (segment is zero-filled by the creator); everyone attaches.
 void* mp4x_shm_attach(void* base, int rank, int p, int64_t slot_bytes, int nthreads, double timeout_s) {
   Shm* s = new Shm;
   s->base = (char*)base;
@@ -478,9 +473,6 @@ void* mp4x_shm_attach(void* base, int rank, int p, int64_t slot_bytes, int nthre
   return s;
 }
 
-// After every rank attached: turn on peer-death detection in the barrier iff every peer is
-// visible in this process's /proc with the start time it published (same pid namespace).
-// Returns 1 when enabled, 0 when not (the barrier then relies on its timeout alone).
 int mp4x_shm_watch_peers(void* h) {
   Shm* s = (Shm*)h;
   s->watch = false;
@@ -498,7 +490,6 @@ void mp4x_shm_detach(void* h) { delete (Shm*)h; }
 
 int mp4x_shm_barrier(void* h) { return shm_barrier((Shm*)h); }
 
-// In-place allreduce of buf[0, n) (elements) — pieces of one slot each.
 int mp4x_shm_allreduce(void* h, int dtype, int op, void* buf, int64_t n) {
   Shm* s = (Shm*)h;
   const int es = esize(dtype);
@@ -534,7 +525,6 @@ int mp4x_shm_allreduce(void* h, int dtype, int op, void* buf, int64_t n) {
   return 0;
 }
 
-// Ragged reduce-scatter: rank r ends with the reduction of every rank's [froms[r], tos[r]).
 int mp4x_shm_reduce_scatter(void* h, int dtype, int op, void* buf, const int64_t* froms, const int64_t* tos) {
   Shm* s = (Shm*)h;
   const int es = esize(dtype);
@@ -565,7 +555,6 @@ int mp4x_shm_reduce_scatter(void* h, int dtype, int op, void* buf, const int64_t
   return 0;
 }
 
-// Ragged allgather: every rank ends with every rank's [froms[j], tos[j]).
 int mp4x_shm_allgather(void* h, int es, void* buf, const int64_t* froms, const int64_t* tos) {
   Shm* s = (Shm*)h;
   int64_t maxc = 0;
@@ -617,29 +606,13 @@ struct alignas(64) TBarrier {
   BarrierWords words() { return BarrierWords{&count, &gen, &abort, &sleepers, n, timeout_s, false}; }
 };
 
-extern "C" void* mp4x_tbarrier_create(int n, double timeout_s) {
-  if (n < 1) return nullptr;
-  TBarrier* b = new TBarrier();
-  b->n = (uint32_t)n;
-  b->timeout_s = timeout_s > 0 ? timeout_s : 1e30;
-  return b;
-}
-
-extern "C" void mp4x_tbarrier_destroy(void* h) { delete (TBarrier*)h; }
-
-extern "C" void mp4x_tbarrier_abort(void* h) {
-  TBarrier* b = (TBarrier*)h;
+static void tbarrier_abort(TBarrier* b) {
   b->abort.store(1, std::memory_order_seq_cst);
   futex_op(&b->gen, FUTEX_WAKE, INT_MAX, nullptr, false);   // sleepers re-check `abort`
 }
 
-extern "C" int mp4x_tbarrier_aborted(void* h) { return (int)((TBarrier*)h)->abort.load(std::memory_order_acquire); }
-
 // 0: released; -1: timed out (the barrier is then aborted for everyone); -2: aborted.
-extern "C" int mp4x_tbarrier_wait(void* h) {
-  TBarrier* b = (TBarrier*)h;
-  return barrier_wait(b->words());
-}
+static int tbarrier_wait(TBarrier* b) { return barrier_wait(b->words()); }
 
 // ---------------------------------------------------------------- native thread-team collectives
 // The thread level of ThreadCommSlave for host arrays, entirely below the GIL: every thread
@@ -704,10 +677,10 @@ extern "C" void mp4x_team_destroy(void* h) { delete (Team*)h; }
 extern "C" int mp4x_team_barrier(void* h, int tid) {
   Team* tm = (Team*)h;
   const uint64_t k = team_enter(tm, tid);
-  return team_leave(tm, tid, k, mp4x_tbarrier_wait(&tm->bar));
+  return team_leave(tm, tid, k, tbarrier_wait(&tm->bar));
 }
-extern "C" int mp4x_team_aborted(void* h) { return mp4x_tbarrier_aborted(&((Team*)h)->bar); }
-extern "C" void mp4x_team_abort(void* h) { mp4x_tbarrier_abort(&((Team*)h)->bar); }
+extern "C" int mp4x_team_aborted(void* h) { return (int)((Team*)h)->bar.abort.load(std::memory_order_acquire); }
+extern "C" void mp4x_team_abort(void* h) { tbarrier_abort(&((Team*)h)->bar); }
 
 static inline void team_chunk(int64_t f, int64_t t, int T, int tid, int64_t* lo, int64_t* hi) {
   const int64_t n = t - f;
@@ -746,15 +719,14 @@ static int team_reduce_chunk(Team* tm, int tid, int64_t f, int64_t t, int dtype,
 static int team_reduce_phase(Team* tm, int tid, void* buf, int64_t f, int64_t t, int dtype, int op, int root,
                              bool spread) {
   tm->slots[tid] = buf;
-  if (int rc = mp4x_tbarrier_wait(&tm->bar)) return rc;
+  if (int rc = tbarrier_wait(&tm->bar)) return rc;
   if (int rc = team_reduce_chunk(tm, tid, f, t, dtype, op, root, spread)) {
-    mp4x_tbarrier_abort(&tm->bar);
+    tbarrier_abort(&tm->bar);
     return rc;
   }
-  return mp4x_tbarrier_wait(&tm->bar);
+  return tbarrier_wait(&tm->bar);
 }
 
-// [f, t) of every thread's buffer reduced into the root thread's buffer (then a barrier).
 extern "C" int mp4x_team_reduce(void* h, int tid, void* buf, int64_t f, int64_t t, int dtype, int op, int root) {
   if (!esize(dtype)) return MP4X_E_UNSUPPORTED;
   Team* tm = (Team*)h;
@@ -762,22 +734,20 @@ extern "C" int mp4x_team_reduce(void* h, int tid, void* buf, int64_t f, int64_t 
   return team_leave(tm, tid, k, team_reduce_phase(tm, tid, buf, f, t, dtype, op, root, false));
 }
 
-// Root's [f, t) copied into every other thread's buffer: publish, barrier, copy, barrier.
 extern "C" int mp4x_team_bcast(void* h, int tid, void* buf, int64_t f, int64_t t, int elem_bytes, int root) {
   Team* tm = (Team*)h;
   const uint64_t k = team_enter(tm, tid);
   tm->slots[tid] = buf;
-  int rc = mp4x_tbarrier_wait(&tm->bar);
+  int rc = tbarrier_wait(&tm->bar);
   if (!rc) {
     if (tid != root && t > f)
       std::memcpy((char*)buf + f * elem_bytes, (const char*)tm->slots[root] + f * elem_bytes, (t - f) * elem_bytes);
-    rc = mp4x_tbarrier_wait(&tm->bar);
+    rc = tbarrier_wait(&tm->bar);
   }
   return team_leave(tm, tid, k, rc);
 }
 
-// Fused thread-level allreduce (slaveNum == 1): publish, barrier, each thread reduces its chunk
-// of every buffer and writes the result into every buffer's chunk, barrier.  Two meetings.
+// ThreadCommSlave takes this one when slaveNum == 1.
 extern "C" int mp4x_team_allreduce(void* h, int tid, void* buf, int64_t f, int64_t t, int dtype, int op) {
   if (!esize(dtype)) return MP4X_E_UNSUPPORTED;
   Team* tm = (Team*)h;

@@ -15,17 +15,7 @@
 #include <thread>
 #include <vector>
 
-#include "mp4x/ops.h"
-
-extern "C" {
-int mp4x_host_reduce(int dtype, int op, void* out, const void* const* ins, int nin, int64_t n, int nthreads);
-void* mp4x_shm_attach(void* base, int rank, int p, int64_t slot_bytes, int nthreads, double timeout_s);
-void mp4x_shm_detach(void* h);
-int mp4x_shm_allreduce(void* h, int dtype, int op, void* buf, int64_t n);
-int mp4x_shm_reduce_scatter(void* h, int dtype, int op, void* buf, const int64_t* froms, const int64_t* tos);
-int mp4x_shm_allgather(void* h, int es, void* buf, const int64_t* froms, const int64_t* tos);
-int mp4x_shm_broadcast(void* h, int es, void* buf, int64_t frm, int64_t to, int root);
-}
+#include "mp4x/host.h"
 
 static double val(int rank, int64_t i) { return (double)((rank * 7 + i * 3) % 11) - 5.0; }
 

@@ -1,9 +1,18 @@
-// mp4x native C API (CDNA4 / gfx950).
+// mp4x native C API (CDNA4 / gfx950): the kernels (csrc/kernels/*.hip).
 //
-// One C ABI shared by every kernel translation unit and called from Python via
-// ctypes (mp4x/ops/native.py).  All entry points are stream-ordered (no host
-// synchronisation, no allocation) so they can be captured in hipGraphs.
-// Return value: 0 on success, otherwise a hipError_t / MP4X_E* code.
+// Three plain-C headers ARE the ABI of the native libraries; every exported mp4x_* function is
+// declared in exactly one of them, with its contract, and every translation unit that defines or
+// calls one includes that header (a definition that disagrees does not compile):
+//   mp4x/ops.h      the kernels of libmp4x_hip.so (this file) + the shared enums and codes
+//   mp4x/runtime.h  the device runtime of libmp4x_hip.so (csrc/runtime/*.hip)
+//   mp4x/host.h     libmp4x_host.so (csrc/host/host_ops.cpp)
+// Python binds them through two ctypes tables, mp4x/ops/hip_sigs.py and mp4x/ops/host_sigs.py;
+// tests/test_native_abi_cpu.py parses the headers and holds tables, headers and the libraries'
+// exports to each other.  So the headers stay flat: one prototype per `;`, no macros around
+// prototypes, no function-pointer parameters.
+//
+// The kernel entry points are stream-ordered (no host synchronisation, no allocation) so they can
+// be captured in hipGraphs.  Return value: 0 on success, otherwise a hipError_t / MP4X_E* code.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -12,14 +21,14 @@
 extern "C" {
 #endif
 
-// Element types — keep in sync with mp4x/operators.py DType.
+// Element types: mp4x/operators.py DType (compared by tests/test_native_abi_cpu.py).
 enum mp4x_dtype {
   MP4X_F64 = 0, MP4X_F32 = 1, MP4X_I64 = 2, MP4X_I32 = 3, MP4X_I16 = 4, MP4X_I8 = 5,
   MP4X_BF16 = 6, MP4X_F16 = 7, MP4X_U8 = 8,
 };
 
-// Reduction operators — keep in sync with mp4x/operators.py OpCode.
-// Reference table: /root/reference/src/main/java/com/fenbi/mp4j/operator/Operators.java:29-353
+// Reduction operators: mp4x/operators.py OpCode (compared by the same test).  The reference's
+// table: src/main/java/com/fenbi/mp4j/operator/Operators.java:29-353.
 enum mp4x_op {
   MP4X_SUM = 0, MP4X_MAX = 1, MP4X_MIN = 2, MP4X_PROD = 3,
   MP4X_BAND = 4, MP4X_BOR = 5, MP4X_BXOR = 6,
@@ -64,6 +73,13 @@ int mp4x_segment_copy(void* dst, const void* src, const int64_t* dev_table, int 
 int mp4x_gather_rows(void* out, const void* in, const int64_t* idx, int64_t nrows, int64_t row_bytes,
                      void* stream);
 
+// Sparse staging: keys[n] (int64) + vals[n][row_bytes] (row_bytes a multiple of 16, 16-byte
+// aligned; NULL when row_bytes == 0) -> dst_vals[n][row_bytes] + dst_keys16[n][16] (the key in
+// the low 8 bytes of a 16-byte vector); keys_from16 reads such vectors back into int64 keys.
+int mp4x_stage_split(const int64_t* keys, const void* vals, int64_t n, int64_t row_bytes, void* dst_vals,
+                     void* dst_keys16, void* stream);
+int mp4x_keys_from16(const void* keys16, int64_t n, int64_t* keys, void* stream);
+
 // ---------------------------------------------------------------- K6 codec (fp8 e4m3, OCP)
 // Block-scaled quantisation: scale[b] = amax(block b) / 448, q = fp8(x / scale).
 // block must be 256 (one wave, 4 elements per lane).  n must be a multiple of 4.
@@ -72,7 +88,6 @@ int mp4x_quant_fp8(int dtype_in, const void* in, int64_t n, uint8_t* q, float* s
 // If q_out != NULL the f32 result is also re-quantised into (q_out, s_out).
 int mp4x_dequant_reduce_fp8(int dtype_out, void* out, const uint8_t* const* qs, const float* const* scales,
                             int nin, int64_t n, int accumulate, uint8_t* q_out, float* s_out, void* stream);
-int mp4x_dequant_fp8(int dtype_out, void* out, const uint8_t* q, const float* scales, int64_t n, void* stream);
 
 // K6b lossless zero suppression.  table (device int64): elem_start[nchunk], elem_len[nchunk],
 // blk_start[nchunk + 1] in 256-element blocks.  Encode: masks[4 * nblk], counts[nblk],
@@ -88,10 +103,12 @@ int mp4x_zs_decode(int elem_bytes, const uint64_t* masks, const int32_t* counts,
 // ---------------------------------------------------------------- K4 / K5 / K7 sparse
 // Owner of each key: dest[i] = (uint64)key[i] % p.  hist[p] += counts (hist zeroed by caller).
 int mp4x_key_owner(const int64_t* keys, int64_t n, int p, int32_t* dest, int32_t* hist, void* stream);
-// Stable radix sort of (key, idx) pairs on bits [begin_bit, end_bit).
+// Stable radix sort of (key, idx) pairs on bits [begin_bit, end_bit).  algo (int64 keys): 0 =
+// rocPRIM's own choice, 1 = onesweep (one pass per 8 bits of [begin_bit, end_bit)).
 size_t mp4x_sort_pairs_temp_bytes(int64_t n, int key_is_i32);
 int mp4x_sort_pairs_i64(const int64_t* keys_in, int64_t* keys_out, const int64_t* idx_in, int64_t* idx_out,
-                        int64_t n, int begin_bit, int end_bit, void* temp, size_t temp_bytes, void* stream);
+                        int64_t n, int begin_bit, int end_bit, int algo, void* temp, size_t temp_bytes,
+                        void* stream);
 int mp4x_sort_pairs_i32key(const int32_t* keys_in, int32_t* keys_out, const int64_t* idx_in, int64_t* idx_out,
                            int64_t n, int begin_bit, int end_bit, void* temp, size_t temp_bytes, void* stream);
 // Fused stable partition by owner ((uint64)key % p, p <= 2048): out_keys / out_vals (rows of
@@ -122,9 +139,44 @@ int mp4x_segment_reduce_rows(int dtype, int op, const int64_t* sorted_keys, cons
                              const void* vals, int64_t dim, int64_t* out_keys, void* out_vals, int32_t* out_count,
                              void* stream);
 
-// ---------------------------------------------------------------- info
-const char* mp4x_version(void);
-int mp4x_device_count(void);
+// K5h reduce-by-key without a sort (hash table).  supported: does the hash path serve
+// (dtype, op)?  1 / 0 (every reduction of the segmented reduce except the FIRST rule, which needs
+// the rank order of arbitrarily long runs).  keys[n], vals[n][dim] -> out_keys[m] (table order),
+// out_vals[m][dim], out_count[m] (optional); m_flag[0] = m, written on the device (stream-ordered;
+// m_flag[1] is zeroed).  out_* must hold n rows; scratch: 256-byte aligned, scratch_bytes(n).
+size_t mp4x_hash_rbk_scratch_bytes(int64_t n);
+int mp4x_hash_rbk_supported(int dtype, int op);
+int mp4x_hash_reduce_by_key(int dtype, int op, const int64_t* keys, int64_t n, const void* vals, int64_t dim,
+                            void* scratch, size_t scratch_bytes, int64_t* out_keys, void* out_vals,
+                            int32_t* out_count, int64_t* m_flag, void* stream);
+// K5d: keys[n] with k / stride - base in [0, T) (e.g. an owner's share of dense ids, stride = p),
+// vals[n][dim] (or NULL: keys only) -> out_keys[m] ascending, out_vals[m][dim] (rows combined in
+// input order: the sort path's result bit for bit), out_count[m] (optional); m_flag[0] = m,
+// m_flag[1] != 0 when the keys were not dense after all (then nothing else is meaningful: use the
+// sort path).
+size_t mp4x_dense_rbk_scratch_bytes(int64_t n, int64_t T);
+int mp4x_dense_reduce_by_key(int dtype, int op, const int64_t* keys, int64_t n, const void* vals, int64_t dim,
+                             int64_t base, int64_t stride, int64_t T, void* scratch, size_t scratch_bytes,
+                             int64_t* out_keys, void* out_vals, int32_t* out_count, int64_t* m_flag, void* stream);
+
+// ---------------------------------------------------------------- errors
+// Reads and clears this thread's last HIP error.  mp4x reports its own failures through return
+// codes; a failed HIP call must not stay "last error" for PyTorch's next kernel-launch check to
+// report as its own (native.check() and the best-effort release paths call this).
+int mp4x_clear_error(void);
+
+// ---------------------------------------------------------------- test / A-B hooks
+// Process-wide switches of the kernel-variant sweeps (tools/bench_kernels.py, bench/, the codec
+// tests); never set by a job.  k1_variant: the K1 kernel form (default 2: tile + nontemporal);
+// k1_grid: its grid cap in blocks (0: one tile per block).  dq_unroll: quant blocks per wave iteration
+// of the dequant-reduce (0: by fan-in); codec_grid: 1 = the codec launches its whole grid (the
+// default), 0 = the capped grid-stride form.  zs_set_twopass: 1 = mask + scan + compact (two reads
+// of the input, the default), 0 = the single-pass encode.
+void mp4x_set_k1_variant(int v);
+void mp4x_set_k1_grid(int64_t cap);
+void mp4x_set_dq_unroll(int du);
+void mp4x_set_codec_grid(int full);
+int mp4x_zs_set_twopass(int on);
 
 #ifdef __cplusplus
 }

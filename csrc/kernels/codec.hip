@@ -633,13 +633,6 @@ extern "C" int mp4x_dequant_reduce_fp8(int dtype_out, void* out, const uint8_t* 
   }
 }
 
-extern "C" int mp4x_dequant_fp8(int dtype_out, void* out, const uint8_t* q, const float* scales, int64_t n,
-                                void* stream) {
-  const uint8_t* qs[1] = {q};
-  const float* ss[1] = {scales};
-  return mp4x_dequant_reduce_fp8(dtype_out, out, qs, ss, 1, n, 0, nullptr, nullptr, stream);
-}
-
 extern "C" size_t mp4x_zs_temp_bytes(int64_t nblk) {
   size_t bytes = 0;
   (void)rocprim::exclusive_scan(nullptr, bytes, (const int32_t*)nullptr, (int64_t*)nullptr, (int64_t)0,
@@ -662,15 +655,11 @@ static int zs_twopass() {
   return g_zs_twopass;
 }
 
-// A/B switch: 1 = mask + scan + compact (two reads of the input), 0 = single-pass encode
 extern "C" int mp4x_zs_set_twopass(int on) {
   g_zs_twopass = on ? 1 : 0;
   return 0;
 }
 
-// table (device int64): elem_start[nchunk], elem_len[nchunk], blk_start[nchunk + 1] (blk_start[j]
-// = sum of ceil(elem_len[i] / 256) for i < j).  offs needs nblk + 1 entries; offs[nblk] = total
-// non-zero words.  vals must hold the worst case (every word non-zero).
 extern "C" int mp4x_zs_encode(int elem_bytes, const void* in, const int64_t* table, int nchunk, int64_t nblk,
                               uint64_t* masks, int32_t* counts, int64_t* offs, void* vals, void* temp,
                               size_t temp_bytes, void* stream) {

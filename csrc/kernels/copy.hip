@@ -104,8 +104,6 @@ __global__ __launch_bounds__(kBlock) void k_keys_from16(const u32x4* __restrict_
 
 using namespace mp4x;
 
-// keys[n] (int64) + vals[n][row_bytes] (row_bytes a multiple of 16, 16-byte aligned; NULL when
-// row_bytes == 0) -> dst_vals[n][row_bytes] + dst_keys16[n][16].
 extern "C" int mp4x_stage_split(const int64_t* keys, const void* vals, int64_t n, int64_t row_bytes, void* dst_vals,
                                 void* dst_keys16, void* stream) {
   if (n <= 0) return 0;

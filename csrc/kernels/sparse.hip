@@ -334,10 +334,9 @@ extern "C" size_t mp4x_sort_pairs_temp_bytes(int64_t n, int key_is_i32) {
   return bytes > ob ? bytes : ob;
 }
 
-// algo: 0 = rocPRIM's own choice, 1 = onesweep (one pass per 8 bits of [begin_bit, end_bit)).
-extern "C" int mp4x_sort_pairs_i64_ex(const int64_t* keys_in, int64_t* keys_out, const int64_t* idx_in,
-                                      int64_t* idx_out, int64_t n, int begin_bit, int end_bit, int algo, void* temp,
-                                      size_t temp_bytes, void* stream) {
+extern "C" int mp4x_sort_pairs_i64(const int64_t* keys_in, int64_t* keys_out, const int64_t* idx_in, int64_t* idx_out,
+                                   int64_t n, int begin_bit, int end_bit, int algo, void* temp, size_t temp_bytes,
+                                   void* stream) {
   if (n <= 0) return 0;
   if (algo == 1)
     return (int)rocprim::radix_sort_pairs<OnesweepSort>(temp, temp_bytes, keys_in, keys_out, idx_in, idx_out,
@@ -345,12 +344,6 @@ extern "C" int mp4x_sort_pairs_i64_ex(const int64_t* keys_in, int64_t* keys_out,
                                                         (hipStream_t)stream);
   return (int)rocprim::radix_sort_pairs(temp, temp_bytes, keys_in, keys_out, idx_in, idx_out, (size_t)n,
                                         (unsigned)begin_bit, (unsigned)end_bit, (hipStream_t)stream);
-}
-
-extern "C" int mp4x_sort_pairs_i64(const int64_t* keys_in, int64_t* keys_out, const int64_t* idx_in, int64_t* idx_out,
-                                   int64_t n, int begin_bit, int end_bit, void* temp, size_t temp_bytes,
-                                   void* stream) {
-  return mp4x_sort_pairs_i64_ex(keys_in, keys_out, idx_in, idx_out, n, begin_bit, end_bit, 0, temp, temp_bytes, stream);
 }
 
 extern "C" int mp4x_sort_pairs_i32key(const int32_t* keys_in, int32_t* keys_out, const int64_t* idx_in,
@@ -432,8 +425,7 @@ PackScratch pack_scratch(void* scratch, size_t scratch_bytes, int64_t n, int p) 
 
 // K4b in two halves, so a caller can exchange the counts before it picks where the packed rows
 // go (the sparse owner exchange scatters them straight into its IPC staging buffer).
-// Count: per-tile owner histogram + scan -> counts[p] (rows per owner) and range[2] (optional: the
-// smallest and largest key; 0, 0 when n == 0).  The scratch then holds the scan for the scatter.
+// Count: per-tile owner histogram + scan; the scratch then holds the scan for the scatter.
 extern "C" int mp4x_partition_pack_count(const int64_t* keys, int64_t n, int p, int64_t* counts, int64_t* range,
                                          void* scratch, size_t scratch_bytes, void* stream) {
   hipStream_t st = (hipStream_t)stream;
@@ -457,10 +449,6 @@ extern "C" int mp4x_partition_pack_count(const int64_t* keys, int64_t n, int p, 
   return (int)hipGetLastError();
 }
 
-// Scatter (after mp4x_partition_pack_count on the same keys, p and scratch): out_keys (key_stride
-// 1: int64[n]; 2: the key half of n 16-byte vectors) / out_vals (rows of row_bytes, 16-B aligned;
-// vals may be NULL) in owner-major, input-stable order; out_perm (optional) = source row of
-// every slot.
 extern "C" int mp4x_partition_pack_scatter(const int64_t* keys, const void* vals, int64_t n, int64_t row_bytes,
                                            int p, int64_t* out_keys, int key_stride, void* out_vals,
                                            int64_t* out_perm, void* scratch, size_t scratch_bytes, void* stream) {
@@ -478,8 +466,6 @@ extern "C" int mp4x_partition_pack_scatter(const int64_t* keys, const void* vals
   return (int)hipGetLastError();
 }
 
-// Both halves: keys[n] (+ rows vals[n][row_bytes]) -> stable-by-owner layout out_keys / out_vals,
-// optional out_perm, counts[p] and range[2] (optional).
 extern "C" int mp4x_partition_pack(const int64_t* keys, const void* vals, int64_t n, int64_t row_bytes, int p,
                                    int64_t* out_keys, void* out_vals, int64_t* out_perm, int64_t* counts,
                                    int64_t* range, void* scratch, size_t scratch_bytes, void* stream) {

@@ -432,13 +432,8 @@ using namespace mp4x;
 
 extern "C" size_t mp4x_hash_rbk_scratch_bytes(int64_t n) { return layout(n < 0 ? 0 : n).total; }
 
-// Does the hash path serve (dtype, op)?  1 / 0.  (Every reduction of the segmented reduce except
-// the FIRST rule, which needs the rank order of arbitrarily long runs.)
 extern "C" int mp4x_hash_rbk_supported(int dtype, int op) { return pair_supported(RowOps{}, dtype, op) == 0; }
 
-// keys[n], vals[n][dim] -> out_keys[m] (table order), out_vals[m][dim], out_count[m] (optional);
-// m_flag[0] = m, written on the device (stream-ordered; m_flag[1] is zeroed).  out_* must hold
-// n rows.
 extern "C" int mp4x_hash_reduce_by_key(int dtype, int op, const int64_t* keys, int64_t n, const void* vals, int64_t dim,
                                        void* scratch, size_t scratch_bytes, int64_t* out_keys, void* out_vals,
                                        int32_t* out_count, int64_t* m_flag, void* stream) {
@@ -470,10 +465,6 @@ extern "C" size_t mp4x_dense_rbk_scratch_bytes(int64_t n, int64_t T) {
   return dense_layout(n < 0 ? 0 : n, T < 1 ? 1 : T).total;
 }
 
-// K5d: keys[n] with k / stride - base in [0, T) (e.g. an owner's share of dense ids, stride = p),
-// vals[n][dim] (or NULL: keys only) -> out_keys[m] ascending, out_vals[m][dim] (rows combined in
-// input order: the sort path's result bit for bit), out_count[m] (optional); m_flag[0] = m, m_flag[1] != 0 when the keys
-// were not dense after all (then nothing else is meaningful: use the sort path).
 extern "C" int mp4x_dense_reduce_by_key(int dtype, int op, const int64_t* keys, int64_t n, const void* vals,
                                         int64_t dim, int64_t base, int64_t stride, int64_t T, void* scratch,
                                         size_t scratch_bytes, int64_t* out_keys, void* out_vals, int32_t* out_count,

@@ -1,44 +1,26 @@
 // _mp4x_launch: the per-call launch of the IPC allreduce kernels without ctypes.
 //
-// A small device allreduce is host-bound (profiles/r4/latency/): ctypes converts each of the 15
-// arguments of mp4x_ipc_allreduce_ex through its argtypes on every call (~2 us of a ~12 us call).
+// A small device allreduce is host-bound (profiles/r4/latency/): ctypes converts each of the
+// arguments of mp4x_ipc_allreduce through its argtypes on every call (~2 us of a ~12 us call).
 // This extension parses them with METH_FASTCALL and calls the SAME exported function of
 // libmp4x_hip.so through a pointer handed over once (``bind``: the address ctypes resolved in the
 // already-loaded library, so release / debug builds and the torch HIP runtime are the ones in use).
-// No HIP headers, no link against the HIP library.
+// No HIP headers, no link against the HIP library: mp4x/runtime.h gives the pointers their types.
 #define PY_SSIZE_T_CLEAN
 #include <Python.h>
 
 #include <cstdint>
 
+#include "mp4x/runtime.h"
+
 namespace {
 
-// mp4x_ipc_allreduce_ex2 (the slot arguments last; 0 / 0 = the single-buffer form)
-using AllreduceEx = int (*)(int algo, int dtype, int op, void* const* data_ptrs, void* const* signal_ptrs, int rank,
-                            int p, int64_t nbytes, const void* src, void* out, uint32_t epoch, int blocks,
-                            const uint32_t* epoch_dev, float scale, void* stream, int64_t slot_base,
-                            int64_t slot_vecs);
-
-AllreduceEx g_allreduce_ex = nullptr;
-
-// mp4x_ipc_fast_allreduce(state, algo, dtype, op, buf, nbytes, blocks, scale, stream): the latency
-// tier's whole per-call path (error words, capture check, epoch, launch) in libmp4x_hip.so.
-using FastAllreduce = int (*)(const void* state, int algo, int dtype, int op, void* buf, int64_t nbytes, int blocks,
-                              float scale, void* stream);
-FastAllreduce g_fast = nullptr;
-
-// mp4x_ipc_fast_plan(state, stage, nstage, pull, npull, src_off, out_off, base, grid_len, buf_vecs,
-// blocks, stream): the same one-call path for a memoised copy plan.
-using FastPlan = int (*)(const void* state, const int64_t* stage, int nstage, const int64_t* pull, int npull,
-                         int64_t src_off, int64_t out_off, void* base, int64_t grid_len, int64_t buf_vecs, int blocks,
-                         void* stream);
-FastPlan g_fast_plan = nullptr;
-
-// mp4x_ipc_fast_rs(state, dtype, op, seg_lo, seg_hi, src_off, out_off, base, blocks, stream): the
-// same for a memoised fused reduce-scatter.
-using FastRs = int (*)(const void* state, int dtype, int op, const int64_t* seg_lo, const int64_t* seg_hi,
-                       int64_t src_off, int64_t out_off, void* base, int blocks, void* stream);
-FastRs g_fast_rs = nullptr;
+// mp4x_ipc_allreduce (the slot arguments last; 0 / 0 = the single-buffer form)
+decltype(&mp4x_ipc_allreduce) g_allreduce_ex = nullptr;
+// The latency tier's whole per-call paths (error words, capture check, epoch, launch).
+decltype(&mp4x_ipc_fast_allreduce) g_fast = nullptr;
+decltype(&mp4x_ipc_fast_plan) g_fast_plan = nullptr;
+decltype(&mp4x_ipc_fast_rs) g_fast_rs = nullptr;
 
 void* as_ptr(PyObject* o) {   // int address, or None -> NULL
   if (o == Py_None) return nullptr;
@@ -48,7 +30,7 @@ void* as_ptr(PyObject* o) {   // int address, or None -> NULL
 PyObject* bind(PyObject*, PyObject* addr) {
   void* f = PyLong_AsVoidPtr(addr);
   if (!f && PyErr_Occurred()) return nullptr;
-  g_allreduce_ex = reinterpret_cast<AllreduceEx>(f);
+  g_allreduce_ex = reinterpret_cast<decltype(g_allreduce_ex)>(f);
   Py_RETURN_NONE;
 }
 
@@ -92,7 +74,7 @@ PyObject* allreduce_ex(PyObject*, PyObject* const* a, Py_ssize_t na) {
 PyObject* bind_fast(PyObject*, PyObject* addr) {
   void* f = PyLong_AsVoidPtr(addr);
   if (!f && PyErr_Occurred()) return nullptr;
-  g_fast = reinterpret_cast<FastAllreduce>(f);
+  g_fast = reinterpret_cast<decltype(g_fast)>(f);
   Py_RETURN_NONE;
 }
 
@@ -110,7 +92,7 @@ PyObject* fast_allreduce(PyObject*, PyObject* const* a, Py_ssize_t na) {
     return nullptr;
   }
   PyObject* const* t = &PyTuple_GET_ITEM(a[0], 0);
-  const void* state = PyLong_AsVoidPtr(t[0]);
+  const FastAr* state = static_cast<const FastAr*>(PyLong_AsVoidPtr(t[0]));
   const int algo = (int)PyLong_AsLong(t[1]);
   const int dtype = (int)PyLong_AsLong(t[2]);
   const int op = (int)PyLong_AsLong(t[3]);
@@ -131,7 +113,7 @@ PyObject* fast_allreduce(PyObject*, PyObject* const* a, Py_ssize_t na) {
 PyObject* bind_fast_plan(PyObject*, PyObject* addr) {
   void* f = PyLong_AsVoidPtr(addr);
   if (!f && PyErr_Occurred()) return nullptr;
-  g_fast_plan = reinterpret_cast<FastPlan>(f);
+  g_fast_plan = reinterpret_cast<decltype(g_fast_plan)>(f);
   Py_RETURN_NONE;
 }
 
@@ -149,7 +131,7 @@ PyObject* fast_plan(PyObject*, PyObject* const* a, Py_ssize_t na) {
     return nullptr;
   }
   PyObject* const* t = &PyTuple_GET_ITEM(a[0], 0);
-  const void* state = PyLong_AsVoidPtr(t[0]);
+  const FastAr* state = static_cast<const FastAr*>(PyLong_AsVoidPtr(t[0]));
   const int64_t* stage = static_cast<const int64_t*>(PyLong_AsVoidPtr(t[1]));
   const int nstage = (int)PyLong_AsLong(t[2]);
   const int64_t* pull = static_cast<const int64_t*>(PyLong_AsVoidPtr(t[3]));
@@ -172,7 +154,7 @@ PyObject* fast_plan(PyObject*, PyObject* const* a, Py_ssize_t na) {
 PyObject* bind_fast_rs(PyObject*, PyObject* addr) {
   void* f = PyLong_AsVoidPtr(addr);
   if (!f && PyErr_Occurred()) return nullptr;
-  g_fast_rs = reinterpret_cast<FastRs>(f);
+  g_fast_rs = reinterpret_cast<decltype(g_fast_rs)>(f);
   Py_RETURN_NONE;
 }
 
@@ -188,7 +170,7 @@ PyObject* fast_rs(PyObject*, PyObject* const* a, Py_ssize_t na) {
     return nullptr;
   }
   PyObject* const* t = &PyTuple_GET_ITEM(a[0], 0);
-  const void* state = PyLong_AsVoidPtr(t[0]);
+  const FastAr* state = static_cast<const FastAr*>(PyLong_AsVoidPtr(t[0]));
   const int dtype = (int)PyLong_AsLong(t[1]);
   const int op = (int)PyLong_AsLong(t[2]);
   const int64_t* lo = static_cast<const int64_t*>(PyLong_AsVoidPtr(t[3]));
@@ -216,7 +198,7 @@ PyMethodDef kMethods[] = {
     {"bind_fast", bind_fast, METH_O, "bind_fast(address of mp4x_ipc_fast_allreduce in the loaded libmp4x_hip.so)"},
     {"fast_allreduce", reinterpret_cast<PyCFunction>(reinterpret_cast<void (*)()>(fast_allreduce)), METH_FASTCALL,
      "fast_allreduce(entry, stream) -> rc"},
-    {"bind", bind, METH_O, "bind(address of mp4x_ipc_allreduce_ex2 in the loaded libmp4x_hip.so)"},
+    {"bind", bind, METH_O, "bind(address of mp4x_ipc_allreduce in the loaded libmp4x_hip.so)"},
     {"allreduce_ex", reinterpret_cast<PyCFunction>(reinterpret_cast<void (*)()>(allreduce_ex)), METH_FASTCALL,
      "allreduce_ex(algo, dtype, op, data_pp, sig_pp, rank, p, nbytes, src, out, epoch, blocks, epoch_dev, scale, "
      "stream) -> rc"},

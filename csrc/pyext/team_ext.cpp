@@ -16,12 +16,7 @@
 #include <cstdint>
 #include <cstring>
 
-extern "C" {
-int mp4x_team_barrier(void* h, int tid);
-int mp4x_team_reduce(void* h, int tid, void* buf, int64_t f, int64_t t, int dtype, int op, int root);
-int mp4x_team_bcast(void* h, int tid, void* buf, int64_t f, int64_t t, int elem_bytes, int root);
-int mp4x_team_allreduce(void* h, int tid, void* buf, int64_t f, int64_t t, int dtype, int op);
-}
+#include "mp4x/host.h"
 
 namespace {
 

@@ -341,7 +341,6 @@ using namespace mp4x;
 
 extern "C" size_t mp4x_ipc_signal_bytes(void) { return sizeof(Signal); }
 
-// Fine-grained, uncached device allocation (signal blocks and IPC data buffers), zeroed.
 extern "C" int mp4x_ipc_alloc(size_t bytes, void** ptr) {
   hipError_t e = hipExtMallocWithFlags(ptr, bytes, hipDeviceMallocUncached);
   if (e != hipSuccess) return (int)e;
@@ -352,10 +351,6 @@ extern "C" int mp4x_ipc_alloc(size_t bytes, void** ptr) {
 
 extern "C" int mp4x_ipc_free(void* ptr) { return (int)hipFree(ptr); }
 
-// Staging data buffer of an IPC instance, zeroed: ``coarse`` = 0 -> fine-grained uncached (the
-// default: peers' reads never meet a stale L2 line); 1 -> plain coarse-grained hipMalloc memory,
-// L2-cached on its home GPU, kept coherent by the kernels' system-scope release / acquire at
-// every barrier (the zero-copy protocol's argument).  MP4X_IPC_DATA_MEM selects it (A/B).
 extern "C" int mp4x_ipc_alloc_data(size_t bytes, int coarse, void** ptr) {
   if (!coarse) return mp4x_ipc_alloc(bytes, ptr);
   hipError_t e = hipMalloc(ptr, bytes);
@@ -365,12 +360,8 @@ extern "C" int mp4x_ipc_alloc_data(size_t bytes, int coarse, void** ptr) {
   return (int)hipDeviceSynchronize();
 }
 
-// Plain (coarse-grained) device allocation, the kind the PyTorch caching allocator makes: the
-// self-test of the zero-copy protocol runs on memory like the caller tensors it will map.
 extern "C" int mp4x_dev_alloc(size_t bytes, void** ptr) { return (int)hipMalloc(ptr, bytes); }
 
-// Pinned host word the kernels can write (mapped, coherent): *host_ptr for the CPU,
-// *dev_ptr for the kernels.  Zeroed.
 extern "C" int mp4x_host_word_alloc(void** host_ptr, void** dev_ptr) {
   hipError_t e = hipHostMalloc(host_ptr, 64, hipHostMallocMapped | hipHostMallocCoherent);
   if (e != hipSuccess) return (int)e;
@@ -380,16 +371,12 @@ extern "C" int mp4x_host_word_alloc(void** host_ptr, void** dev_ptr) {
 
 extern "C" int mp4x_host_word_free(void* host_ptr) { return (int)hipHostFree(host_ptr); }
 
-// Register the host-visible error word of a signal block (device address from
-// mp4x_host_word_alloc; nullptr to detach).
 extern "C" int mp4x_ipc_set_host_error(void* signal, void* dev_word) {
   const uint64_t v = (uint64_t)(uintptr_t)dev_word;
   hipError_t e = hipMemcpy((char*)signal + offsetof(Signal, host_err), &v, sizeof(v), hipMemcpyHostToDevice);
   return (int)e;
 }
 
-// Barrier spin bound of the kernels that use `signal` (this rank's own Signal block), in seconds.
-// Stream-ordered on `stream` (kernels queued before it keep the previous bound).
 extern "C" int mp4x_ipc_set_spin(void* signal, double seconds, void* stream) {
   if (!(seconds > 0.0) || !signal) return MP4X_E_BADARG;
   const uint64_t ticks = (uint64_t)(seconds * 1.0e8);   // the stream is synchronised below
@@ -399,16 +386,11 @@ extern "C" int mp4x_ipc_set_spin(void* signal, double seconds, void* stream) {
   return (int)hipStreamSynchronize((hipStream_t)stream);
 }
 
-// Bump the device epoch counter of a graph-capturable instance (stream-ordered: the next IPC
-// kernel on `stream` reads the new epoch; see resolve_epoch).
 extern "C" int mp4x_ipc_bump_epoch(uint32_t* epoch_dev, void* stream) {
   hipLaunchKernelGGL(k_ipc_bump_epoch, dim3(1), dim3(1), 0, (hipStream_t)stream, epoch_dev);
   return (int)hipGetLastError();
 }
 
-// PCI bus id of the current device: ranks compare them to detect a GPU shared by several
-// ranks (single-GPU rehearsal), where the per-block barriers need every rank's blocks
-// co-resident and the block count must shrink accordingly.
 extern "C" int mp4x_device_pci_id(char* buf, int len) {
   int dev = 0;
   hipError_t e = hipGetDevice(&dev);
@@ -418,8 +400,6 @@ extern "C" int mp4x_device_pci_id(char* buf, int len) {
 
 extern "C" int mp4x_ipc_handle_size(void) { return (int)sizeof(hipIpcMemHandle_t); }
 
-// Base and size of the allocation that contains `ptr` (IPC handles name whole allocations:
-// a caller tensor inside a caching-allocator segment is exported as (segment handle, offset)).
 extern "C" int mp4x_mem_range(void* ptr, void** base, size_t* size) {
   hipDeviceptr_t b = nullptr;
   size_t sz = 0;
@@ -445,13 +425,6 @@ extern "C" int mp4x_memcpy_async(void* dst, const void* src, size_t bytes, void*
   return (int)hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, (hipStream_t)stream);
 }
 
-extern "C" int mp4x_ipc_read_error(void* signal, uint32_t* err) {
-  return (int)hipMemcpy(err, (char*)signal + offsetof(Signal, error), 4, hipMemcpyDeviceToHost);
-}
-
-// The error word read on `stream` (a private non-blocking stream, so a poll from the collective
-// watchdog thread never serialises with the caller's streams); clear != 0 resets it after the
-// read, so one timed-out barrier is reported once instead of poisoning every later check.
 extern "C" int mp4x_ipc_error_word(void* signal, uint32_t* err, int clear, void* stream) {
   hipStream_t st = (hipStream_t)stream;
   char* w = (char*)signal + offsetof(Signal, error);
@@ -460,9 +433,7 @@ extern "C" int mp4x_ipc_error_word(void* signal, uint32_t* err, int clear, void*
   if (e != hipSuccess) return (int)e;
   return (int)hipStreamSynchronize(st);
 }
-// All-gather of ragged segments: seg_lo/seg_hi[p] (host arrays, 16-B vectors from the buffer
-// base); every rank stages its own segment at its offset; out (the same layout, 16-B aligned)
-// receives every peer's segment.
+
 extern "C" int mp4x_ipc_allgather(void* const* data_ptrs, void* const* signal_ptrs, int rank, int p,
                                   const int64_t* seg_lo, const int64_t* seg_hi, void* out, uint32_t epoch, int blocks,
                                   const uint32_t* epoch_dev, void* stream) {
@@ -492,9 +463,6 @@ extern "C" int mp4x_ipc_allgather(void* const* data_ptrs, void* const* signal_pt
 #undef MP4X_AG_CASE
 }
 
-// Fused fp8 two-shot allreduce of one piece.  Every rank has already quantised its input into
-// its own buffer (q bytes at 0, f32 scales at `soff`, p * cb quant blocks, blocks past the input
-// zeroed); `out` (dtype = f32 / bf16 / f16, 16-B aligned) receives n elements.
 extern "C" int mp4x_ipc_fp8_allreduce(int dtype, void* const* data_ptrs, void* const* signal_ptrs, int rank, int p,
                                       int64_t cb, int64_t soff, void* out, int64_t n, uint32_t epoch, int blocks,
                                       const uint32_t* epoch_dev, float scale, void* stream) {
@@ -524,10 +492,6 @@ extern "C" int mp4x_memset_async(void* dst, int value, size_t bytes, void* strea
   return (int)hipMemsetAsync(dst, value, bytes, (hipStream_t)stream);
 }
 
-// Copy plan (see k_ipc_copy_plan).  stage / pull: n x {src_off, dst_off, len, peer} int64
-// quadruples in 16-byte vectors; `grid_len` (vectors) must be rank-independent — the largest
-// item of any rank — so every rank launches the same grid.
-// Every refusal of mp4x_ipc_copy_plan (the latency fast path runs it before its epoch moves).
 extern "C" int mp4x_ipc_copy_plan_check(int rank, int p, const int64_t* stage, int nstage, const int64_t* pull,
                                         int npull, const void* src, const void* out, int64_t buf_vecs) {
   if (p < 2 || p > kIpcMaxRanks || rank < 0 || rank >= p) return MP4X_E_BADARG;
@@ -570,10 +534,6 @@ extern "C" int mp4x_ipc_copy_plan(void* const* data_ptrs, void* const* signal_pt
   return (int)hipGetLastError();
 }
 
-
-// Blocks per CU the occupancy API admits for the data-movement kernels (family 0 = the ragged
-// all-gather k_ipc_gather<p>, 1 = the copy plan) and the fused fp8 two-shot (2 = wide, 3 = narrow;
-// dtype = the output dtype): the shared-GPU co-residency budget (mp4x/parallel/occupancy.py).
 extern "C" int mp4x_ipc_occupancy_misc(int family, int dtype, int p, int* blocks_per_cu) {
   int m = 1 << 30;
   int e = 0;

@@ -99,20 +99,8 @@ __global__ __launch_bounds__(kIpcThreads) void k_ipc_twoshot(IpcPtrs P, Signal* 
 
 using namespace mp4x;
 
-// algo 0 = one-shot, 1 = two-shot.  data_ptrs / signal_ptrs: p entries (own rank included,
-// peers as mapped by mp4x_ipc_open_handle).  nbytes must be a multiple of 16.
-// epoch_dev == NULL: `epoch` (host counter) is used.  epoch_dev != NULL: graph-capturable form,
-// the kernel reads the epoch from device memory (bump it with mp4x_ipc_bump_epoch first).
-// src != NULL: this rank's input (16-byte aligned) is copied into its own buffer INSIDE the
-// kernel (fused copy-in: one launch per call); NULL: already staged, or zero-copy (the data
-// pointers are the registered caller tensors and out == data_ptrs[rank]).  scale != 1: the
-// reduced value is multiplied by it before it is stored (fused average; float dtypes only).
-// op: any operator of the reference table valid for dtype (MP4X_E_UNSUPPORTED otherwise).
-// slot_base / slot_vecs (16-byte vectors; one- and two-shot): the double-buffered slots (see
-// k_ipc_oneshot); 0 = the single-buffer form with its end barrier.  A slotted call needs src (the
-// fused copy-in: the staging target depends on the device-side epoch) and nbytes <= a slot.
 namespace {
-// Everything mp4x_ipc_allreduce_ex2 refuses, checked without launching: the fast path
+// Everything mp4x_ipc_allreduce refuses, checked without launching: the fast path
 // (mp4x_ipc_fast_allreduce) runs it BEFORE its epoch moves, so a refused call leaves this rank's
 // epoch where its peers expect it; after it only a HIP launch error remains.
 int ar_check(int algo, int dtype, int op, int rank, int p, int64_t nbytes, const void* src, const void* out,
@@ -126,10 +114,10 @@ int ar_check(int algo, int dtype, int op, int rank, int p, int64_t nbytes, const
 }
 }  // namespace
 
-extern "C" int mp4x_ipc_allreduce_ex2(int algo, int dtype, int op, void* const* data_ptrs, void* const* signal_ptrs,
-                                      int rank, int p, int64_t nbytes, const void* src, void* out, uint32_t epoch,
-                                      int blocks, const uint32_t* epoch_dev, float scale, void* stream,
-                                      int64_t slot_base, int64_t slot_vecs) {
+extern "C" int mp4x_ipc_allreduce(int algo, int dtype, int op, void* const* data_ptrs, void* const* signal_ptrs,
+                                  int rank, int p, int64_t nbytes, const void* src, void* out, uint32_t epoch,
+                                  int blocks, const uint32_t* epoch_dev, float scale, void* stream,
+                                  int64_t slot_base, int64_t slot_vecs) {
   if (int e = ar_check(algo, dtype, op, rank, p, nbytes, src, out, scale, slot_base, slot_vecs)) return e;
   IpcPtrs P;
   if (int e = ipc_prepare(data_ptrs, signal_ptrs, rank, p, &P)) return e;
@@ -164,34 +152,9 @@ extern "C" int mp4x_ipc_allreduce_ex2(int algo, int dtype, int op, void* const* 
   });
 }
 
-// The latency tier's whole per-call host path in ONE native call (VERDICT r4 Next #5: 4.7 us of a
-// 10 us 4 KiB allreduce was interpreter time above the bare launch).  The Python entry
-// (ProcessCommSlave.allreduceArray) looks its call shape up in the engine's memo and hands over
-// the memoised launch; everything the Python path did per call happens here:
-//   * the fail-stop check: every IPC instance's pinned host error word (an earlier collective
-//     that timed out fails the next call: MP4X_E_FAILED_EARLIER, the caller raises);
-//   * the capture check: a stream being captured needs the device-epoch form (MP4X_E_CAPTURING);
-//   * every argument refusal of the launcher (MP4X_E_BADARG / MP4X_E_UNSUPPORTED);
-//   * the communicator's stream order (order.hip: a call on another stream than the previous
-//     one first waits for it);
-//   * the epoch bump, in the instance's epoch box (the same word IpcAllreduce.epoch reads);
-//   * the launch (mp4x_ipc_allreduce_ex: fused copy-in, in place, fused scale).
-// Every refusal comes BEFORE the epoch moves (1001-1004: nothing happened, the caller may take
-// the full path).  A launch that fails AFTER it (a HIP error) leaves this rank at the same epoch
-// as its peers, whose kernels of this call then time out at their start barrier: that is
-// consistent, so the epoch is NOT rolled back; instead the instance's own host error word gets
-// code 5, and this rank's next call fails at once (raise_if_failed) instead of waiting for them.
-struct FastAr {
-  const uint32_t* herr[8];   // pinned host error words of the engine's instances (nullptr ends the list)
-  uint32_t* epoch;           // the instance's epoch box
-  void* const* data_ptrs;    // every rank's staging buffer
-  void* const* signal_ptrs;  // every rank's signal block
-  int32_t rank, p;
-  int64_t slot_base, slot_vecs;   // the double-buffered slots of the one- / two-shot (0: none)
-  StreamOrder* order;        // the communicator's stream-order guard (nullptr: none)
-  uint32_t* own_err;         // this instance's pinned host error word (launch failures: code 5)
-};
-
+// The latency tier's whole per-call host path in ONE native call (mp4x/runtime.h "latency fast
+// paths": 4.7 us of a 10 us 4 KiB allreduce was interpreter time above the bare launch), in three
+// steps shared by the three entry points.
 constexpr uint32_t kLaunchFailedErr = 5u;
 
 namespace {
@@ -235,22 +198,12 @@ extern "C" int mp4x_ipc_fast_allreduce(const FastAr* s, int algo, int dtype, int
   if (int e = ar_check(algo, dtype, op, s->rank, s->p, nbytes, buf, buf, scale, sb, sv)) return e;
   uint32_t e = 0;
   if (int rc = fast_begin(s, stream, &e)) return rc;
-  return fast_end(s, mp4x_ipc_allreduce_ex2(algo, dtype, op, s->data_ptrs, s->signal_ptrs, s->rank, s->p, nbytes, buf,
-                                            buf, e, blocks, nullptr, scale, stream, sb, sv));
+  return fast_end(s, mp4x_ipc_allreduce(algo, dtype, op, s->data_ptrs, s->signal_ptrs, s->rank, s->p, nbytes, buf,
+                                        buf, e, blocks, nullptr, scale, stream, sb, sv));
 }
 
-extern "C" int mp4x_ipc_copy_plan(void* const* data_ptrs, void* const* signal_ptrs, int rank, int p,
-                                  const int64_t* stage, int nstage, const int64_t* pull, int npull, const void* src,
-                                  void* out, int64_t grid_len, int64_t buf_vecs, uint32_t epoch, int blocks,
-                                  const uint32_t* epoch_dev, void* stream);
-extern "C" int mp4x_ipc_copy_plan_check(int rank, int p, const int64_t* stage, int nstage, const int64_t* pull,
-                                        int npull, const void* src, const void* out, int64_t buf_vecs);
-
 // The same one-call path for a memoised copy plan (the latency tier of broadcast / gather /
-// scatter / all-gather, csrc/runtime/ipc.hip k_ipc_copy_plan): error words, capture check, every
-// refusal of the launcher — all before the epoch moves — then the stream order, the epoch bump
-// and the launch.  src_off / out_off: byte offsets of the plan's source / output from `base` (the
-// caller's tensor), or -1 for none.
+// scatter / all-gather, csrc/runtime/ipc.hip k_ipc_copy_plan).
 extern "C" int mp4x_ipc_fast_plan(const FastAr* s, const int64_t* stage, int nstage, const int64_t* pull, int npull,
                                   int64_t src_off, int64_t out_off, void* base, int64_t grid_len, int64_t buf_vecs,
                                   int blocks, void* stream) {
@@ -266,16 +219,8 @@ extern "C" int mp4x_ipc_fast_plan(const FastAr* s, const int64_t* stage, int nst
                                         out, grid_len, buf_vecs, e, blocks, nullptr, stream));
 }
 
-extern "C" int mp4x_ipc_reduce_scatter_from(int dtype, int op, void* const* data_ptrs, void* const* signal_ptrs,
-                                            int rank, int p, const int64_t* seg_lo, const int64_t* seg_hi,
-                                            const void* src, void* out, uint32_t epoch, int blocks,
-                                            const uint32_t* epoch_dev, void* stream);
-extern "C" int mp4x_ipc_reduce_scatter_from_check(int dtype, int op, int rank, int p, const int64_t* seg_lo,
-                                                  const int64_t* seg_hi, const void* src, const void* out);
-
-// The same one-call path for a memoised fused reduce-scatter (csrc/runtime/ipc_rs.hip: the
-// kernel stages this rank's range and writes its segment in place).  seg_lo / seg_hi: p segment
-// bounds in 16-byte vectors from the range start; src_off / out_off: byte offsets from `base`.
+// The same for a memoised fused reduce-scatter (csrc/runtime/ipc_rs.hip: the kernel stages this
+// rank's range and writes its segment in place).
 extern "C" int mp4x_ipc_fast_rs(const FastAr* s, int dtype, int op, const int64_t* seg_lo, const int64_t* seg_hi,
                                 int64_t src_off, int64_t out_off, void* base, int blocks, void* stream) {
   if (int e = fast_prologue(s)) return e;
@@ -289,26 +234,8 @@ extern "C" int mp4x_ipc_fast_rs(const FastAr* s, int dtype, int op, const int64_
                                                   seg_hi, b + src_off, b + out_off, e, blocks, nullptr, stream));
 }
 
-extern "C" int mp4x_ipc_allreduce_ex(int algo, int dtype, int op, void* const* data_ptrs, void* const* signal_ptrs,
-                                     int rank, int p, int64_t nbytes, const void* src, void* out, uint32_t epoch,
-                                     int blocks, const uint32_t* epoch_dev, float scale, void* stream) {
-  return mp4x_ipc_allreduce_ex2(algo, dtype, op, data_ptrs, signal_ptrs, rank, p, nbytes, src, out, epoch, blocks,
-                                epoch_dev, scale, stream, 0, 0);
-}
-
-// The pre-staged form (no fused copy-in, no scale).
-extern "C" int mp4x_ipc_allreduce(int algo, int dtype, int op, void* const* data_ptrs, void* const* signal_ptrs,
-                                  int rank, int p, int64_t nbytes, void* out, uint32_t epoch, int blocks,
-                                  const uint32_t* epoch_dev, void* stream) {
-  return mp4x_ipc_allreduce_ex(algo, dtype, op, data_ptrs, signal_ptrs, rank, p, nbytes, nullptr, out, epoch, blocks,
-                               epoch_dev, 1.0f, stream);
-}
-
-// Does the IPC allreduce have a kernel for (dtype, op)?  1 / 0.
 extern "C" int mp4x_ipc_op_supported(int dtype, int op) { return op_supported(dtype, op) == 0; }
 
-// Blocks per CU the occupancy API admits for the kernel a call of (algo, dtype, op, p) launches
-// (the shared-GPU co-residency budget, mp4x/parallel/occupancy.py).
 extern "C" int mp4x_ipc_occupancy_ar(int algo, int dtype, int op, int p, int* blocks_per_cu) {
   int m = 1 << 30;
   int e = with_dtype(dtype, [&](auto dtc) {

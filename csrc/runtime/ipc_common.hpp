@@ -13,7 +13,7 @@
 //              remote bytes per rank — the bandwidth-optimal full-mesh schedule.
 //
 // Reference analogue: the fused recv+reduce of the ring reduce-scatter, for EVERY operator of
-// every primitive type (/root/reference/src/main/java/com/fenbi/mp4j/operator/Operators.java:29-353,
+// every primitive type (src/main/java/com/fenbi/mp4j/operator/Operators.java:29-353,
 // hot loops DoubleOperand.java:196, ShortOperand.java:194, ByteOperand.java:193) and the
 // small-message RPC allreduce (ProcessCommSlave.java:1776-1926) — here as one kernel.
 //
@@ -59,8 +59,26 @@
 #include <hip/hip_runtime.h>
 
 #include "../kernels/common.hpp"
+#include "mp4x/runtime.h"
+
+// The per-communicator stream-order guard (csrc/runtime/order.hip, mp4x/parallel/order.py): the
+// device-side total order of ONE communicator's collectives across the caller's streams.  Opaque
+// in mp4x/runtime.h; field order is the ctypes layout of mp4x.parallel.order.StreamOrder.
+struct mp4x_stream_order {
+  void* last;            // hipStream_t of the communicator's previous launch (when have_last)
+  void* ev;              // hipEvent_t, created at the first stream switch
+  void* cap_stream;      // the stream of the current graph capture's launches (when cap_have)
+  uint64_t cap_id;       // that capture's id
+  uint64_t switches;     // stream switches joined so far (statistics, tests)
+  int32_t have_last;
+  int32_t cap_have;
+  int32_t disabled;      // MP4X_TEST_NO_STREAM_ORDER=1: tests only (shows the guard has teeth)
+  int32_t pad;
+};
 
 namespace mp4x {
+
+using StreamOrder = ::mp4x_stream_order;
 
 constexpr int kIpcMaxRanks = 8;
 constexpr int kIpcMaxBlocks = 256;
@@ -125,24 +143,6 @@ __device__ __forceinline__ uint32_t dbg_flags_of(const Signal* self) {
 }
 
 constexpr uint64_t kDefaultSpinTicks = 600ull * 100000000ull;   // 600 s at 100 MHz
-
-// The per-communicator stream-order guard (csrc/runtime/order.hip, mp4x/parallel/order.py): the
-// device-side total order of ONE communicator's collectives across the caller's streams.  Field
-// order is the ctypes layout of mp4x.parallel.order.StreamOrder.
-struct StreamOrder {
-  void* last;            // hipStream_t of the communicator's previous launch (when have_last)
-  void* ev;              // hipEvent_t, created at the first stream switch
-  void* cap_stream;      // the stream of the current graph capture's launches (when cap_have)
-  uint64_t cap_id;       // that capture's id
-  uint64_t switches;     // stream switches joined so far (statistics, tests)
-  int32_t have_last;
-  int32_t cap_have;
-  int32_t disabled;      // MP4X_TEST_NO_STREAM_ORDER=1: tests only (shows the guard has teeth)
-  int32_t pad;
-};
-// 0, or MP4X_E_STREAM_SWITCH / a HIP error: see order.hip (mp4x_order_enter: the caller knows the
-// stream is not being captured).
-extern "C" int mp4x_order_enter(StreamOrder* o, void* stream);
 
 struct IpcPtrs {
   const void* data[kIpcMaxRanks];   // every rank's data buffer (own one included)

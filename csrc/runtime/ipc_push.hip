@@ -67,10 +67,7 @@ __global__ __launch_bounds__(kIpcThreads) void k_ipc_twoshot_push(IpcPtrs P, Scr
 
 using namespace mp4x;
 
-// Zero-copy PUSH two-shot (see k_ipc_twoshot_push): data_ptrs = every rank's registered tensor
-// (this rank's own included; the result replaces it), scratch_ptrs = every rank's receive
-// scratch of at least (p - 1) * ceil(nbytes / 16 / p) 16-byte vectors.  Any operator of the
-// reference table valid for dtype.
+// k_ipc_twoshot_push.
 extern "C" int mp4x_ipc_allreduce_push(int dtype, int op, void* const* data_ptrs, void* const* scratch_ptrs,
                                        void* const* signal_ptrs, int rank, int p, int64_t nbytes, uint32_t epoch,
                                        int blocks, const uint32_t* epoch_dev, float scale, void* stream) {

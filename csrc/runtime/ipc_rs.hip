@@ -60,8 +60,6 @@ static int launch_rs(int dtype, int op, const IpcPtrs& P, Signal* self, int rank
 
 using namespace mp4x;
 
-// Reduce-scatter over staged buffers: out (16-B aligned) receives vectors [vec_lo, vec_hi) of
-// the op-reduction of all p buffers.  Every rank stages its WHOLE range before the call.
 extern "C" int mp4x_ipc_reduce_scatter(int dtype, int op, void* const* data_ptrs, void* const* signal_ptrs, int rank,
                                        int p, int64_t vec_lo, int64_t vec_hi, void* out, uint32_t epoch, int blocks,
                                        const uint32_t* epoch_dev, void* stream) {
@@ -73,11 +71,6 @@ extern "C" int mp4x_ipc_reduce_scatter(int dtype, int op, void* const* data_ptrs
                    ipc_blocks(blocks, vec_hi - vec_lo), (hipStream_t)stream, o);
 }
 
-// Reduce-scatter with fused staging: `src` (16-B aligned) holds this rank's whole range laid out
-// like the buffer (vector offsets seg_lo/seg_hi per rank, relative to src and to the buffer);
-// this rank's reduced segment goes straight to `out` (16-B aligned) at out[v - lo].  One launch.
-// Every refusal of mp4x_ipc_reduce_scatter_from (the latency fast path runs it before its epoch
-// moves): alignment, rank range, segment bounds, and the (dtype, op) pair.
 extern "C" int mp4x_ipc_reduce_scatter_from_check(int dtype, int op, int rank, int p, const int64_t* seg_lo,
                                                   const int64_t* seg_hi, const void* src, const void* out) {
   if (!src || ((uintptr_t)src & 15) || ((uintptr_t)out & 15)) return MP4X_E_BADARG;

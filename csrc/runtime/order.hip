@@ -29,9 +29,6 @@
 
 using namespace mp4x;
 
-// `capturing`: 0 = the caller knows the stream is not being captured (the fast paths checked it),
-// 1 = it is, -1 = unknown (queried here).  The steady state (same stream as the previous launch,
-// not capturing) is one compare.
 extern "C" int mp4x_order_enter_ex(StreamOrder* o, void* stream, int capturing) {
   if (!o) return 0;
   if (capturing == 0 && o->have_last && o->last == stream) return 0;      // the steady state
@@ -80,7 +77,6 @@ extern "C" int mp4x_order_enter_ex(StreamOrder* o, void* stream, int capturing) 
 
 extern "C" int mp4x_order_enter(StreamOrder* o, void* stream) { return mp4x_order_enter_ex(o, stream, 0); }
 
-// Release the guard's event (the communicator is closing; its streams were drained).
 extern "C" int mp4x_order_release(StreamOrder* o) {
   if (!o || !o->ev) return 0;
   hipError_t e = hipEventDestroy((hipEvent_t)o->ev);

@@ -9,14 +9,8 @@
 
 #include <cstdint>
 
-// For every ordered pair (a, b) of the n visible devices fill row-major n*n arrays:
-//   link[a*n+b]   HSA link type (4 = xGMI, 2 = PCIe; -1 = unknown / a == b)
-//   hops[a*n+b]   hop count (0 on the diagonal)
-//   access[a*n+b] hipDevP2PAttrAccessSupported
-//   rank[a*n+b]   hipDevP2PAttrPerformanceRank
-//   atomics[a*n+b] hipDevP2PAttrNativeAtomicSupported
-// Returns the number of devices written (<= cap), or -(hipError) on failure.  Touches no
-// device memory; safe to call before any allocation.
+#include "mp4x/runtime.h"
+
 extern "C" int mp4x_topology(int cap, int* link, int* hops, int* access, int* rank, int* atomics) {
   int n = 0;
   hipError_t e = hipGetDeviceCount(&n);

@@ -23,6 +23,8 @@
 #include <cstring>
 #include <unistd.h>
 
+#include "mp4x/runtime.h"
+
 namespace {
 
 hipMemAllocationProp make_prop(int dev) {
@@ -88,7 +90,6 @@ int teardown(void* va, size_t chunk, int n, const uint64_t* handles, size_t rese
 
 }  // namespace
 
-// Recommended allocation granularity (bytes) of the current device for fd-exportable memory.
 extern "C" int mp4x_vmm_granularity(size_t* gran) {
   int dev = 0;
   hipError_t e = hipGetDevice(&dev);
@@ -97,10 +98,6 @@ extern "C" int mp4x_vmm_granularity(size_t* gran) {
   return (int)hipMemGetAllocationGranularity(gran, &prop, hipMemAllocationGranularityRecommended);
 }
 
-// Allocate ``n`` chunks of ``chunk`` bytes (granularity multiple) mapped back to back at a
-// fresh VA range.  ``fds`` (n entries) get one exported POSIX fd per chunk when ``fds`` is not
-// null; ``handles`` (n entries) get the generic allocation handles.  On failure everything
-// created so far is released and the fds closed.
 extern "C" int mp4x_vmm_create(size_t chunk, int n, void** va_out, uint64_t* handles, int* fds) {
   int dev = 0;
   hipError_t e = hipGetDevice(&dev);
@@ -146,9 +143,6 @@ extern "C" int mp4x_vmm_create(size_t chunk, int n, void** va_out, uint64_t* han
   return 0;
 }
 
-// Import a peer's ``n`` chunk fds and map them back to back at a fresh VA range of this
-// process, read/write for the current device.  The fds are NOT closed here (the caller owns
-// them; the imported handles keep the memory alive).
 extern "C" int mp4x_vmm_import(const int* fds, size_t chunk, int n, void** va_out, uint64_t* handles) {
   int dev = 0;
   hipError_t e = hipGetDevice(&dev);
@@ -183,14 +177,11 @@ extern "C" int mp4x_vmm_import(const int* fds, size_t chunk, int n, void** va_ou
   return 0;
 }
 
-// Unmap + release ``n`` chunks mapped at ``va`` and free the VA range (own or imported).
 extern "C" int mp4x_vmm_free(void* va, size_t chunk, int n, const uint64_t* handles) {
   return teardown(va, chunk, n, handles, chunk * (size_t)n);
 }
 
-// Unmap + release the chunks but keep the VA range reserved for the rest of the process: no
-// later reservation lands on these addresses, and no hipMemAddressFree happens (see the chunk
-// pool below for why).  MP4X_VMM_POLICY fresh_va / keep_*_va, parallel/ipc.py mem_free.
+// MP4X_VMM_POLICY fresh_va / keep_*_va, parallel/ipc.py mem_free (see the chunk pool below for why).
 extern "C" int mp4x_vmm_release_keep_va(void* va, size_t chunk, int n, const uint64_t* handles) {
   return teardown(va, chunk, n, handles, 0);
 }
@@ -203,7 +194,6 @@ extern "C" int mp4x_vmm_release_keep_va(void* va, size_t chunk, int n, const uin
 // physical chunks for reuse (parallel/vmm.py ChunkPool) and never frees a VA range: an allocation
 // maps pooled chunks into a fresh range, memFree only unmaps.
 
-// One physical chunk of ``bytes`` (granularity multiple); ``fd`` (nullable) gets its dmabuf fd.
 extern "C" int mp4x_vmm_chunk_create(size_t bytes, uint64_t* handle, int* fd) {
   int dev = 0;
   hipError_t e = hipGetDevice(&dev);
@@ -224,7 +214,6 @@ extern "C" int mp4x_vmm_chunk_create(size_t bytes, uint64_t* handle, int* fd) {
   return 0;
 }
 
-// A peer's chunk from its dmabuf fd (the fd stays the caller's).
 extern "C" int mp4x_vmm_chunk_import(int fd, uint64_t* handle) {
   hipMemGenericAllocationHandle_t h;
   int v = fd;     // read THROUGH the pointer by this runtime (see mp4x_vmm_import)
@@ -238,9 +227,6 @@ extern "C" int mp4x_vmm_chunk_release(uint64_t handle) {
   return (int)hipMemRelease((hipMemGenericAllocationHandle_t)(uintptr_t)handle);
 }
 
-// Reserve a fresh range of sum(sizes) bytes and map ``n`` chunks back to back, read/write for the
-// current device.  On failure the chunks mapped so far are unmapped and the range is left
-// reserved (never freed, see above); *va_out gets it either way (0 if the reservation failed).
 extern "C" int mp4x_vmm_map_chunks(const uint64_t* handles, const size_t* sizes, int n, void** va_out) {
   int dev = 0;
   hipError_t e = hipGetDevice(&dev);
@@ -276,7 +262,6 @@ extern "C" int mp4x_vmm_map_chunks(const uint64_t* handles, const size_t* sizes,
   return (int)e;
 }
 
-// Unmap ``n`` chunks mapped back to back at ``va`` (the range stays reserved, the chunks alive).
 extern "C" int mp4x_vmm_unmap_chunks(void* va, const size_t* sizes, int n) {
   int first = 0;
   size_t off = 0;
@@ -288,16 +273,13 @@ extern "C" int mp4x_vmm_unmap_chunks(void* va, const size_t* sizes, int n) {
   return first;
 }
 
-// Turn the address hint mode on / off; returns the cursor (the next hinted address, 0 = none yet).
 extern "C" uint64_t mp4x_vmm_va_hint(int on) {
   g_hint_on = on != 0;
   return (uint64_t)g_cursor;
 }
 
-// System-scope release on every XCD: each workgroup's lane 0 issues a release fence at system
-// scope (L2 write-back of that XCD's dirty lines), with enough workgroups that every XCD runs
-// several of them.  Makes what earlier kernels wrote into coarse-grained memory visible to
-// readers that do not go through this GPU's L2 (a peer over xGMI, or another mapping).
+// Each workgroup's lane 0 issues a release fence at system scope (L2 write-back of that XCD's
+// dirty lines), with enough workgroups that every XCD runs several of them.
 __global__ void __launch_bounds__(64) k_release_all_xcds() {
   if (threadIdx.x == 0) __builtin_amdgcn_fence(__ATOMIC_RELEASE, "");
 }

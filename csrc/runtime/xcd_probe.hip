@@ -112,9 +112,7 @@ __global__ __launch_bounds__(kProbeThreads) void k_xcd_probe(u32x4* data, uint32
 }  // namespace
 }  // namespace mp4x
 
-// Run the probe on caller-provided device buffers: `data` (8 * region_vecs 16-byte vectors, any
-// contents), `flags` (512 u32, zeroed by this call), `out` (34 u32, zeroed by this call).  `mask`:
-// kDbgNoRelease | kDbgNoAcquire leave the producer's release / the consumer's acquire out.
+// mask: kDbgNoRelease | kDbgNoAcquire.
 extern "C" int mp4x_xcd_probe(void* data, void* flags, void* out, int64_t region_vecs, int rounds, uint32_t mask,
                               double spin_s, void* stream) {
   using namespace mp4x;
@@ -131,8 +129,6 @@ extern "C" int mp4x_xcd_probe(void* data, void* flags, void* out, int64_t region
   return (int)hipGetLastError();
 }
 
-// The debug flags of an IPC instance's own Signal block (kDbgNoRelease / kDbgNoAcquire): read by
-// block_barrier in the debug build (libmp4x_hip_debug.so) only; the release kernels ignore them.
 extern "C" int mp4x_ipc_set_debug(void* signal, uint32_t flags) {
   using namespace mp4x;
   if (!signal) return MP4X_E_BADARG;

@@ -8,17 +8,8 @@ what the zero-copy forms rely on across GPUs (tests/test_coherence_gpu.py; VERDI
 """
 from __future__ import annotations
 
-import ctypes
-
 from . import native
-from .native import c_int, c_int64, c_void_p, check, stream_ptr
-
-native.register_signatures({
-    "mp4x_xcd_probe": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int, ctypes.c_uint32, ctypes.c_double,
-                               c_void_p]),
-    "mp4x_ipc_set_debug": (c_int, [c_void_p, ctypes.c_uint32]),
-    "mp4x_debug_build": (c_int, []),
-})
+from .native import check, stream_ptr
 
 NO_RELEASE = 1      # kDbgNoRelease: the producer's release fence left out
 NO_ACQUIRE = 2      # kDbgNoAcquire: the consumer's acquire fence left out

@@ -16,6 +16,7 @@ from . import native
 from .native import check, ptr_array, stream_ptr
 
 QBLOCK = 256
+MAX_NIN = 8      # MP4X_MAX_NIN (csrc/include/mp4x/ops.h): inputs per launch, chained beyond
 
 
 def _dev_check(*ts):
@@ -189,7 +190,7 @@ def dequant_reduce_fp8(out: Optional[torch.Tensor], qs: Sequence[torch.Tensor], 
         if q_out.numel() < nblk * QBLOCK or s_out is None or s_out.numel() < nblk:
             raise ValueError(f"dequant_reduce_fp8: q_out needs whole blocks ({nblk * QBLOCK} bytes for n = {n}) "
                              f"and s_out {nblk}")
-    if out is None and len(qs) > 8:
+    if out is None and len(qs) > MAX_NIN:
         # the kernel keeps its partial sums in `out`: without one, chain through an f32 temporary
         # (every launch would otherwise start from zero and q_out hold the last launch's sum only)
         if n <= 0:
@@ -202,7 +203,7 @@ def dequant_reduce_fp8(out: Optional[torch.Tensor], qs: Sequence[torch.Tensor], 
     done = 0
     first = True
     while done < len(qs):
-        k = min(8, len(qs) - done)
+        k = min(MAX_NIN, len(qs) - done)
         qp, k1 = ptr_array([t.data_ptr() for t in qs[done:done + k]])
         sp, k2 = ptr_array([t.data_ptr() for t in ss[done:done + k]])
         last = done + k == len(qs)
@@ -432,8 +433,8 @@ def sort_pairs(keys: torch.Tensor, idx: Optional[torch.Tensor] = None, end_bit: 
         return ko, io
     if algo is None:
         algo = sort_algo(n, eb)
-    check(lib.mp4x_sort_pairs_i64_ex(keys.data_ptr(), ko.data_ptr(), idx.data_ptr(), io.data_ptr(), n, 0, eb, int(algo),
-                                     temp.data_ptr(), tb, stream_ptr(stream)), "mp4x_sort_pairs")
+    check(lib.mp4x_sort_pairs_i64(keys.data_ptr(), ko.data_ptr(), idx.data_ptr(), io.data_ptr(), n, 0, eb, int(algo),
+                                  temp.data_ptr(), tb, stream_ptr(stream)), "mp4x_sort_pairs")
     return ko, io
 
 

@@ -17,6 +17,7 @@ import threading
 from typing import Sequence
 
 from ..exceptions import NativeError, Mp4jException
+from .hip_sigs import HIP_SIGS
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 NATIVE_DIR = os.path.join(os.path.dirname(_HERE), "_native")
@@ -29,6 +30,10 @@ c_void_p, c_int, c_int64, c_double, c_size_t = ctypes.c_void_p, ctypes.c_int, ct
 PP = ctypes.POINTER(ctypes.c_void_p)
 
 
+# MP4X_E_* of csrc/include/mp4x/ops.h (tests/test_native_abi_cpu.py compares names and values)
+E_BADARG, E_UNSUPPORTED, E_FAILED_EARLIER, E_CAPTURING, E_STREAM_SWITCH = 1001, 1002, 1003, 1004, 1005
+
+
 class NativeUnavailable(Mp4jException):
     pass
 
@@ -37,77 +42,13 @@ _lock = threading.RLock()    # launch_ext() calls hip() under it
 _hip = None
 _host = None
 
-_HIP_SIGS = {
-    "mp4x_reduce": (c_int, [c_int, c_int, c_void_p, PP, c_int, c_int64, c_void_p]),
-    "mp4x_reduce_strided": (c_int, [c_int, c_int, c_void_p, c_void_p, c_int64, c_int, c_int64, c_void_p]),
-    "mp4x_scale": (c_int, [c_int, c_void_p, c_void_p, c_double, c_int64, c_void_p]),
-    "mp4x_segment_copy": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int64, c_void_p]),
-    "mp4x_gather_rows": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p]),
-    "mp4x_quant_fp8": (c_int, [c_int, c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
-    "mp4x_dequant_reduce_fp8": (c_int, [c_int, c_void_p, PP, PP, c_int, c_int64, c_int, c_void_p, c_void_p, c_void_p]),
-    "mp4x_dequant_fp8": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
-    "mp4x_zs_temp_bytes": (c_size_t, [c_int64]),
-    "mp4x_zs_set_twopass": (c_int, [c_int]),
-    "mp4x_zs_encode": (c_int, [c_int, c_void_p, c_void_p, c_int, c_int64, c_void_p, c_void_p, c_void_p, c_void_p,
-                               c_void_p, c_size_t, c_void_p]),
-    "mp4x_zs_decode": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int64, c_void_p, c_void_p,
-                               c_void_p, c_size_t, c_void_p]),
-    "mp4x_key_owner": (c_int, [c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p]),
-    "mp4x_sort_pairs_temp_bytes": (c_size_t, [c_int64, c_int]),
-    "mp4x_sort_pairs_i64": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p, c_size_t, c_void_p]),
-    "mp4x_sort_pairs_i64_ex": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_void_p,
-                                       c_size_t, c_void_p]),
-    "mp4x_sort_pairs_i32key": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p, c_size_t, c_void_p]),
-    "mp4x_partition_pack_scratch_bytes": (c_size_t, [c_int64, c_int]),
-    "mp4x_partition_pack": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int, c_void_p, c_void_p, c_void_p,
-                                    c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
-    "mp4x_partition_pack_count": (c_int, [c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
-    "mp4x_partition_pack_scatter": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int, c_void_p, c_int, c_void_p,
-                                            c_void_p, c_void_p, c_size_t, c_void_p]),
-    "mp4x_rle_temp_bytes": (c_size_t, [c_int64]),
-    "mp4x_run_starts": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
-    "mp4x_segment_reduce_rows": (c_int, [c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64,
-                                         c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),
-    "mp4x_stage_split": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p]),
-    "mp4x_keys_from16": (c_int, [c_void_p, c_int64, c_void_p, c_void_p]),
-    "mp4x_hash_rbk_scratch_bytes": (c_size_t, [c_int64]),
-    "mp4x_hash_rbk_supported": (c_int, [c_int, c_int]),
-    "mp4x_hash_reduce_by_key": (c_int, [c_int, c_int, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_size_t,
-                                        c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
-    "mp4x_dense_rbk_scratch_bytes": (c_size_t, [c_int64, c_int64]),
-    "mp4x_dense_reduce_by_key": (c_int, [c_int, c_int, c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int64, c_int64,
-                                         c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
-    "mp4x_set_k1_variant": (None, [c_int]),
-    "mp4x_set_dq_unroll": (None, [c_int]),
-    "mp4x_set_codec_grid": (None, [c_int]),
-    "mp4x_set_k1_grid": (None, [c_int64]),
-    "mp4x_version": (ctypes.c_char_p, []),
-    "mp4x_clear_error": (c_int, []),
-    "mp4x_device_count": (c_int, []),
-}
-
-_OPTIONAL = set()
-
-
 def _bind(lib, sigs):
+    """Give every function of ``sigs`` its C signature; a library that lacks one (a stale build)
+    fails here with the symbol's name."""
     for name, (res, args) in sigs.items():
-        try:
-            f = getattr(lib, name)
-        except AttributeError:
-            if name in _OPTIONAL:
-                continue
-            raise
+        f = getattr(lib, name)
         f.restype = res
         f.argtypes = args
-
-
-def register_signatures(sigs: dict, optional: bool = False) -> None:
-    """Extra modules (device runtime) add their C signatures here before first load."""
-    _HIP_SIGS.update(sigs)
-    if optional:
-        _OPTIONAL.update(sigs.keys())
-    if _hip is not None:
-        _bind(_hip, sigs)
 
 
 def hip():
@@ -121,7 +62,7 @@ def hip():
             if not os.path.exists(HIP_LIB):
                 raise NativeUnavailable(f"{HIP_LIB} not built: run `python tools/build_native.py`")
             lib = ctypes.CDLL(HIP_LIB, mode=ctypes.RTLD_GLOBAL)
-            _bind(lib, _HIP_SIGS)
+            _bind(lib, HIP_SIGS)
             _hip = lib
     return _hip
 
@@ -243,16 +184,11 @@ def launch_ext():
                     try:
                         lib = hip()
                         mod = _load_ext("_mp4x_launch")
-                        mod.bind(ctypes.cast(lib.mp4x_ipc_allreduce_ex2, ctypes.c_void_p).value)
-                        fast = getattr(lib, "mp4x_ipc_fast_allreduce", None)
-                        if fast is not None and hasattr(mod, "bind_fast"):
-                            mod.bind_fast(ctypes.cast(fast, ctypes.c_void_p).value)
-                        plan = getattr(lib, "mp4x_ipc_fast_plan", None)
-                        if plan is not None and hasattr(mod, "bind_fast_plan"):
-                            mod.bind_fast_plan(ctypes.cast(plan, ctypes.c_void_p).value)
-                        frs = getattr(lib, "mp4x_ipc_fast_rs", None)
-                        if frs is not None and hasattr(mod, "bind_fast_rs"):
-                            mod.bind_fast_rs(ctypes.cast(frs, ctypes.c_void_p).value)
+                        for bind, fn in ((mod.bind, lib.mp4x_ipc_allreduce),
+                                         (mod.bind_fast, lib.mp4x_ipc_fast_allreduce),
+                                         (mod.bind_fast_plan, lib.mp4x_ipc_fast_plan),
+                                         (mod.bind_fast_rs, lib.mp4x_ipc_fast_rs)):
+                            bind(ctypes.cast(fn, ctypes.c_void_p).value)
                     except Exception:   # noqa: BLE001 — ctypes path stays
                         mod = False
                 _launch_ext = mod
@@ -274,17 +210,14 @@ def clear_hip_error() -> int:
     lib = _hip
     if lib is None:
         return 0
-    try:
-        return int(lib.mp4x_clear_error())
-    except Exception:   # noqa: BLE001 — an older library without the symbol
-        return 0
+    return int(lib.mp4x_clear_error())
 
 
 def check(rc: int, where: str) -> None:
     if rc != 0:
         if rc < 1000:
             clear_hip_error()
-        msgs = {1001: "bad argument", 1002: "unsupported dtype/op"}
+        msgs = {E_BADARG: "bad argument", E_UNSUPPORTED: "unsupported dtype/op"}
         raise NativeError(where, rc, msgs.get(rc, "hip error"))
 
 

@@ -24,57 +24,8 @@ import torch
 from ..exceptions import Mp4jException
 from ..operators import DType, OpCode, dtype_of_torch
 from ..ops import native
-from ..ops.native import check, capturing_now, ptr_array, stream_ptr, c_int, c_int64, c_void_p, c_size_t, PP
+from ..ops.native import check, capturing_now, ptr_array, stream_ptr, c_void_p, c_size_t
 from . import occupancy
-
-native.register_signatures({
-    "mp4x_ipc_signal_bytes": (c_size_t, []),
-    "mp4x_ipc_alloc": (c_int, [c_size_t, ctypes.POINTER(c_void_p)]),
-    "mp4x_ipc_alloc_data": (c_int, [c_size_t, c_int, ctypes.POINTER(c_void_p)]),
-    "mp4x_ipc_free": (c_int, [c_void_p]),
-    "mp4x_host_word_alloc": (c_int, [ctypes.POINTER(c_void_p), ctypes.POINTER(c_void_p)]),
-    "mp4x_host_word_free": (c_int, [c_void_p]),
-    "mp4x_ipc_set_host_error": (c_int, [c_void_p, c_void_p]),
-    "mp4x_ipc_set_spin": (c_int, [c_void_p, ctypes.c_double, c_void_p]),
-    "mp4x_ipc_op_supported": (c_int, [c_int, c_int]),
-    "mp4x_ipc_occupancy_ar": (c_int, [c_int, c_int, c_int, c_int, ctypes.POINTER(c_int)]),
-    "mp4x_ipc_occupancy_push": (c_int, [c_int, c_int, c_int, ctypes.POINTER(c_int)]),
-    "mp4x_ipc_occupancy_rs": (c_int, [c_int, c_int, c_int, ctypes.POINTER(c_int)]),
-    "mp4x_ipc_occupancy_misc": (c_int, [c_int, c_int, c_int, ctypes.POINTER(c_int)]),
-    "mp4x_mem_range": (c_int, [c_void_p, ctypes.POINTER(c_void_p), ctypes.POINTER(c_size_t)]),
-    "mp4x_dev_alloc": (c_int, [c_size_t, ctypes.POINTER(c_void_p)]),
-    "mp4x_ipc_allreduce_push": (c_int, [c_int, c_int, PP, PP, PP, c_int, c_int, c_int64, ctypes.c_uint32, c_int,
-                                        c_void_p, ctypes.c_float, c_void_p]),
-    "mp4x_ipc_handle_size": (c_int, []),
-    "mp4x_ipc_get_handle": (c_int, [c_void_p, c_void_p]),
-    "mp4x_ipc_open_handle": (c_int, [c_void_p, ctypes.POINTER(c_void_p)]),
-    "mp4x_ipc_close_handle": (c_int, [c_void_p]),
-    "mp4x_ipc_read_error": (c_int, [c_void_p, ctypes.POINTER(ctypes.c_uint32)]),
-    "mp4x_ipc_error_word": (c_int, [c_void_p, ctypes.POINTER(ctypes.c_uint32), c_int, c_void_p]),
-    "mp4x_ipc_fp8_allreduce": (c_int, [c_int, PP, PP, c_int, c_int, c_int64, c_int64, c_void_p, c_int64,
-                                       ctypes.c_uint32, c_int, c_void_p, ctypes.c_float, c_void_p]),
-    "mp4x_memset_async": (c_int, [c_void_p, c_int, c_size_t, c_void_p]),
-    "mp4x_memcpy_async": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p]),
-    "mp4x_ipc_allreduce": (c_int, [c_int, c_int, c_int, PP, PP, c_int, c_int, c_int64, c_void_p, ctypes.c_uint32,
-                                   c_int, c_void_p, c_void_p]),
-    "mp4x_ipc_allreduce_ex": (c_int, [c_int, c_int, c_int, PP, PP, c_int, c_int, c_int64, c_void_p, c_void_p,
-                                      ctypes.c_uint32, c_int, c_void_p, ctypes.c_float, c_void_p]),
-    "mp4x_ipc_allreduce_ex2": (c_int, [c_int, c_int, c_int, PP, PP, c_int, c_int, c_int64, c_void_p, c_void_p,
-                                       ctypes.c_uint32, c_int, c_void_p, ctypes.c_float, c_void_p, c_int64, c_int64]),
-    "mp4x_ipc_reduce_scatter_from": (c_int, [c_int, c_int, PP, PP, c_int, c_int, ctypes.POINTER(c_int64),
-                                             ctypes.POINTER(c_int64), c_void_p, c_void_p, ctypes.c_uint32, c_int,
-                                             c_void_p, c_void_p]),
-    "mp4x_ipc_bump_epoch": (c_int, [c_void_p, c_void_p]),
-    "mp4x_ipc_copy_plan_check": (c_int, [c_int, c_int, ctypes.POINTER(c_int64), c_int, ctypes.POINTER(c_int64), c_int,
-                                         c_void_p, c_void_p, c_int64]),
-    "mp4x_ipc_copy_plan": (c_int, [PP, PP, c_int, c_int, ctypes.POINTER(c_int64), c_int, ctypes.POINTER(c_int64), c_int,
-                                   c_void_p, c_void_p, c_int64, c_int64, ctypes.c_uint32, c_int, c_void_p, c_void_p]),
-    "mp4x_device_pci_id": (c_int, [ctypes.c_char_p, c_int]),
-    "mp4x_ipc_reduce_scatter": (c_int, [c_int, c_int, PP, PP, c_int, c_int, c_int64, c_int64, c_void_p,
-                                        ctypes.c_uint32, c_int, c_void_p, c_void_p]),
-    "mp4x_ipc_allgather": (c_int, [PP, PP, c_int, c_int, ctypes.POINTER(c_int64), ctypes.POINTER(c_int64),
-                                   c_void_p, ctypes.c_uint32, c_int, c_void_p, c_void_p]),
-})
 
 LOG = logging.getLogger("mp4x.ipc")
 
@@ -235,8 +186,8 @@ def _agree(comm, rank, obj, is_bad):
 
 
 class FastAr(ctypes.Structure):
-    """ctypes layout of the latency fast paths' per-instance state (csrc/runtime/ipc_ar.hip
-    ``FastAr``)."""
+    """ctypes layout of the latency fast paths' per-instance state (``FastAr`` in
+    csrc/include/mp4x/runtime.h; tests/test_native_abi_cpu.py compares the two)."""
     _fields_ = [("herr", c_void_p * 8), ("epoch", c_void_p), ("data_ptrs", c_void_p),
                 ("signal_ptrs", c_void_p), ("rank", ctypes.c_int32), ("p", ctypes.c_int32),
                 ("slot_base", ctypes.c_int64), ("slot_vecs", ctypes.c_int64), ("order", c_void_p),
@@ -654,9 +605,9 @@ class IpcAllreduce(IpcForms):
                 rc = lx.allreduce_ex(algo, dt, code, self._pp_data_addr, self._pp_sig_addr, self.rank, self.p, m,
                                      sp + off if fused else None, dp + off, self.epoch, blocks, edev, scale, st, sb, sv)
             else:
-                rc = self.lib.mp4x_ipc_allreduce_ex2(algo, dt, code, self._pp_data[0], self._pp_sig[0], self.rank,
-                                                     self.p, m, sp + off if fused else None, dp + off, self.epoch,
-                                                     blocks, edev, scale, st, sb, sv)
+                rc = self.lib.mp4x_ipc_allreduce(algo, dt, code, self._pp_data[0], self._pp_sig[0], self.rank,
+                                                 self.p, m, sp + off if fused else None, dp + off, self.epoch,
+                                                 blocks, edev, scale, st, sb, sv)
             check(rc, "mp4x_ipc_allreduce")
             off += m
         return out
@@ -694,8 +645,8 @@ class IpcAllreduce(IpcForms):
             main.wait_event(ev)
             self._next_epoch(ms, False)
             pp = self._pp_hi[0] if slot else self._pp_data[0]
-            check(self.lib.mp4x_ipc_allreduce_ex(algo, dt, int(op.code), pp, self._pp_sig[0], self.rank, self.p, m,
-                                                 None, dst.data_ptr() + off, self.epoch, blocks, edev, scale, ms),
+            check(self.lib.mp4x_ipc_allreduce(algo, dt, int(op.code), pp, self._pp_sig[0], self.rank, self.p, m,
+                                              None, dst.data_ptr() + off, self.epoch, blocks, edev, scale, ms, 0, 0),
                   "mp4x_ipc_allreduce")
             kd = torch.cuda.Event()
             kd.record(main)
@@ -1275,9 +1226,9 @@ class IpcAllreduce(IpcForms):
                                  self._pp_sig_addr, self.rank, self.p, total, None, dst, self.epoch | ZC_TAG, blocks,
                                  edev, scale, st)
         else:
-            rc = self.lib.mp4x_ipc_allreduce_ex(TWOSHOT, int(dtype_of_torch(dtype)), int(op.code), pp[0],
-                                                self._pp_sig[0], self.rank, self.p, total, None, dst,
-                                                self.epoch | ZC_TAG, blocks, edev, scale, st)
+            rc = self.lib.mp4x_ipc_allreduce(TWOSHOT, int(dtype_of_torch(dtype)), int(op.code), pp[0],
+                                             self._pp_sig[0], self.rank, self.p, total, None, dst,
+                                             self.epoch | ZC_TAG, blocks, edev, scale, st, 0, 0)
         check(rc, "mp4x_ipc_allreduce(zero-copy)")
 
     def _peer_pp(self, peers):

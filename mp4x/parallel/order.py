@@ -27,17 +27,11 @@ import os
 
 from ..ops import native
 
-native.register_signatures({
-    "mp4x_order_enter": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p]),
-    "mp4x_order_enter_ex": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int]),
-    "mp4x_order_release": (ctypes.c_int, [ctypes.c_void_p]),
-})
-
-STREAM_SWITCH = 1005      # MP4X_E_STREAM_SWITCH (csrc/include/mp4x/ops.h)
+STREAM_SWITCH = native.E_STREAM_SWITCH
 
 
 class StreamOrder(ctypes.Structure):
-    """ctypes layout of ``mp4x::StreamOrder`` (csrc/runtime/ipc_common.hpp)."""
+    """ctypes layout of ``mp4x_stream_order`` (csrc/runtime/ipc_common.hpp)."""
     _fields_ = [("last", ctypes.c_void_p), ("ev", ctypes.c_void_p), ("cap_stream", ctypes.c_void_p),
                 ("cap_id", ctypes.c_uint64), ("switches", ctypes.c_uint64), ("have_last", ctypes.c_int32),
                 ("cap_have", ctypes.c_int32), ("disabled", ctypes.c_int32), ("pad", ctypes.c_int32)]

@@ -36,6 +36,7 @@ from ..control.protocol import local_ip
 from ..exceptions import Mp4jException, RangeError
 from ..operands import Operand, Operands, DEFAULT_SERIALIZER
 from ..operators import CustomOperator
+from ..ops import native
 from ..utils.commutils import CommUtils
 from ..utils.hashing import owner_of
 from .host_engine import HostEngine, choose_allreduce
@@ -48,7 +49,7 @@ LOG = logging.getLogger("mp4x.comm")
 # (csrc/include/mp4x/ops.h): the call goes on to the full path.  Any other nonzero code is a HIP
 # error AFTER the epoch moved — raised at once (falling back would bump the epoch a
 # second time and leave this rank a call ahead of its peers).
-_NOT_LAUNCHED = frozenset((1001, 1002, 1003, 1004))
+_NOT_LAUNCHED = frozenset((native.E_BADARG, native.E_UNSUPPORTED, native.E_FAILED_EARLIER, native.E_CAPTURING))
 
 
 def _fast_ok(rc: int, where: str) -> bool:
@@ -58,7 +59,6 @@ def _fast_ok(rc: int, where: str) -> bool:
         return True
     if rc in _NOT_LAUNCHED:
         return False
-    from ..ops import native
     native.check(rc, where)
     return False
 

@@ -27,25 +27,7 @@ import torch
 
 from ..exceptions import Mp4jException
 from ..ops import native
-from ..ops.native import check, c_int, c_size_t, c_void_p
-
-_U64P = ctypes.POINTER(ctypes.c_uint64)
-_INTP = ctypes.POINTER(ctypes.c_int)
-
-native.register_signatures({
-    "mp4x_vmm_granularity": (c_int, [ctypes.POINTER(c_size_t)]),
-    "mp4x_vmm_create": (c_int, [c_size_t, c_int, ctypes.POINTER(c_void_p), _U64P, _INTP]),
-    "mp4x_vmm_import": (c_int, [_INTP, c_size_t, c_int, ctypes.POINTER(c_void_p), _U64P]),
-    "mp4x_vmm_free": (c_int, [c_void_p, c_size_t, c_int, _U64P]),
-    "mp4x_vmm_release_keep_va": (c_int, [c_void_p, c_size_t, c_int, _U64P]),
-    "mp4x_vmm_va_hint": (ctypes.c_uint64, [c_int]),
-    "mp4x_vmm_chunk_create": (c_int, [c_size_t, _U64P, _INTP]),
-    "mp4x_vmm_chunk_import": (c_int, [c_int, _U64P]),
-    "mp4x_vmm_chunk_release": (c_int, [ctypes.c_uint64]),
-    "mp4x_vmm_map_chunks": (c_int, [_U64P, ctypes.POINTER(c_size_t), c_int, ctypes.POINTER(c_void_p)]),
-    "mp4x_vmm_unmap_chunks": (c_int, [c_void_p, ctypes.POINTER(c_size_t), c_int]),
-    "mp4x_release_all": (c_int, [c_void_p]),
-})
+from ..ops.native import check, c_size_t, c_void_p
 
 DEFAULT_CHUNK = 512 << 20
 _BIG_FRAG = 2 << 20

@@ -19,20 +19,6 @@ LINK_NAMES = {0: "hypertransport", 1: "qpi", 2: "pcie", 3: "infiniband", 4: "xgm
 XGMI = 4
 _MAX_DEVICES = 64
 
-_sig_done = False
-
-
-def _lib():
-    global _sig_done
-    from ..ops import native
-    lib = native.hip()
-    if not _sig_done:
-        ip = ctypes.POINTER(ctypes.c_int)
-        native.register_signatures({"mp4x_topology": (ctypes.c_int, [ctypes.c_int, ip, ip, ip, ip, ip])})
-        _sig_done = True
-    return lib
-
-
 def probe() -> Optional[Dict[str, List[List[int]]]]:
     """Raw n x n matrices of the visible devices (``link``, ``hops``, ``access``, ``perf_rank``,
     ``atomics``), or None without a GPU / native library."""
@@ -40,7 +26,8 @@ def probe() -> Optional[Dict[str, List[List[int]]]]:
         import torch
         if not torch.cuda.is_available():
             return None
-        lib = _lib()
+        from ..ops import native
+        lib = native.hip()
     except Exception:   # noqa: BLE001 — CPU container, library not built
         return None
     cap = _MAX_DEVICES

@@ -1,5 +1,5 @@
 """The ctypes-free launcher (csrc/pyext/launch_ext.cpp) passes every argument of
-mp4x_ipc_allreduce_ex2 through unchanged (the 15-argument form with slots 0 / 0, or the
+mp4x_ipc_allreduce through unchanged (the 15-argument form with slots 0 / 0, or the
 17-argument form with the one-shot's double-buffered slots): bound here to a ctypes callback with
 the same C signature (CPU, no HIP) that records what it receives."""
 import ctypes

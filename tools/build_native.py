@@ -199,7 +199,8 @@ def build_pyext(host_so):
     out = os.path.join(OUT, "_mp4x_team" + sysconfig.get_config_var("EXT_SUFFIX"))
     if newer(src, out, headers()) or os.path.getmtime(host_so) > os.path.getmtime(out):
         run(["g++", "-O2", "-std=c++17", "-fPIC", "-Wall", "-shared", "-I", sysconfig.get_paths()["include"],
-             src, "-o", out, "-L", OUT, "-l:libmp4x_host.so", "-Wl,-rpath,$ORIGIN"])
+             "-I", os.path.join(CSRC, "include"), src, "-o", out, "-L", OUT, "-l:libmp4x_host.so",
+             "-Wl,-rpath,$ORIGIN"])
         print("  g++  ", os.path.relpath(src, ROOT), "->", os.path.relpath(out, ROOT))
     return out
 
@@ -209,7 +210,7 @@ def build_hostmapext():
     import sysconfig
     src = os.path.join(CSRC, "pyext", "hostmap_ext.cpp")
     out = os.path.join(OUT, "_mp4x_hostmap" + sysconfig.get_config_var("EXT_SUFFIX"))
-    if os.path.exists(src) and newer(src, out, []):
+    if os.path.exists(src) and newer(src, out, headers()):
         import numpy
         run(["g++", "-O2", "-std=c++17", "-fPIC", "-Wall", "-shared", "-I", sysconfig.get_paths()["include"],
              "-I", numpy.get_include(), src, "-o", out])
@@ -219,13 +220,14 @@ def build_hostmapext():
 
 def build_launchext():
     """``_mp4x_launch``: plain CPython extension, the ctypes-free per-call launch of the IPC
-    allreduce (csrc/pyext/launch_ext.cpp; calls libmp4x_hip.so through a bound pointer)."""
+    allreduce (csrc/pyext/launch_ext.cpp; calls libmp4x_hip.so through bound pointers typed by
+    csrc/include/mp4x/runtime.h)."""
     import sysconfig
     src = os.path.join(CSRC, "pyext", "launch_ext.cpp")
     out = os.path.join(OUT, "_mp4x_launch" + sysconfig.get_config_var("EXT_SUFFIX"))
-    if os.path.exists(src) and newer(src, out, []):
+    if os.path.exists(src) and newer(src, out, headers()):
         run(["g++", "-O2", "-std=c++17", "-fPIC", "-Wall", "-shared", "-I", sysconfig.get_paths()["include"],
-             src, "-o", out])
+             "-I", os.path.join(CSRC, "include"), src, "-o", out])
         print("  g++  ", os.path.relpath(src, ROOT), "->", os.path.relpath(out, ROOT))
     return out
 
@@ -241,7 +243,7 @@ def build_mapext():
     import torch
     tinc = os.path.join(os.path.dirname(tl), "include")
     out = os.path.join(OUT, "_mp4x_map" + sysconfig.get_config_var("EXT_SUFFIX"))
-    if newer(src, out, []):
+    if newer(src, out, headers()):
         abi = int(bool(torch._C._GLIBCXX_USE_CXX11_ABI))
         run(["g++", "-O2", "-std=c++17", "-fPIC", "-Wall", "-shared", f"-D_GLIBCXX_USE_CXX11_ABI={abi}",
              "-I", sysconfig.get_paths()["include"], "-isystem", tinc,
