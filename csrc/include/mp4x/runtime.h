@@ -98,6 +98,30 @@ int mp4x_ipc_allreduce_push(int dtype, int op, void* const* data_ptrs, void* con
 int mp4x_ipc_fp8_allreduce(int dtype, void* const* data_ptrs, void* const* signal_ptrs, int rank, int p, int64_t cb,
                            int64_t soff, void* out, int64_t n, uint32_t epoch, int blocks,
                            const uint32_t* epoch_dev, float scale, void* stream);
+// The halves of the fp8 two-shot as collectives over ragged per-rank segments, one piece per call
+// (dtype = f32 / bf16 / f16; the quantise into the own buffer ran just before on `stream`).
+// Segment bounds are elements, multiples of 4; soff (16-B aligned, past the q bytes) is where the
+// f32 scales start in EVERY rank's buffer; blocks <= 0 = a grid from the largest share of any
+// rank.  _check: every refusal of the call without launching; the launcher runs it first.
+// Reduce-scatter: every rank quantised the piece's whole range, `nblk` quant blocks counted from
+// the piece's first element; seg_lo / seg_hi[p] = every rank's segment from that element (in
+// ascending order, inside the nblk blocks); `out` (16-B aligned) = the address of that element in
+// this rank's tensor.  Writes seg_lo[rank] .. seg_hi[rank] only: the f32 sum in rank order of all
+// p dequantised buffers, stored with one rounding.
+int mp4x_ipc_fp8_reduce_scatter(int dtype, void* const* data_ptrs, void* const* signal_ptrs, int rank, int p,
+                                int64_t nblk, int64_t soff, const int64_t* seg_lo, const int64_t* seg_hi, void* out,
+                                uint32_t epoch, int blocks, const uint32_t* epoch_dev, void* stream);
+int mp4x_ipc_fp8_reduce_scatter_check(int dtype, int rank, int p, int64_t nblk, int64_t soff, const int64_t* seg_lo,
+                                      const int64_t* seg_hi, const void* out);
+// All-gather: rank k quantised ITS segment on a block grid counted from the segment's start (at
+// most `maxblk` blocks, the largest segment's); seg_lo / seg_hi[p] = where every rank's segment
+// lands in `out` (16-B aligned; elements from it).  Every segment, the own one included, is
+// dequantised into out, so all ranks hold the same bytes.
+int mp4x_ipc_fp8_allgather(int dtype, void* const* data_ptrs, void* const* signal_ptrs, int rank, int p,
+                           int64_t maxblk, int64_t soff, const int64_t* seg_lo, const int64_t* seg_hi, void* out,
+                           uint32_t epoch, int blocks, const uint32_t* epoch_dev, void* stream);
+int mp4x_ipc_fp8_allgather_check(int dtype, int rank, int p, int64_t maxblk, int64_t soff, const int64_t* seg_lo,
+                                 const int64_t* seg_hi, const void* out);
 // Does the IPC allreduce have a kernel for (dtype, op)?  1 / 0.
 int mp4x_ipc_op_supported(int dtype, int op);
 
@@ -138,7 +162,8 @@ int mp4x_ipc_copy_plan_check(int rank, int p, const int64_t* stage, int nstage, 
 // ---------------------------------------------------------------- occupancy
 // Blocks per CU the occupancy API admits for the kernel such a call launches: the shared-GPU
 // co-residency budget (mp4x/parallel/occupancy.py).  _misc families: 0 = the ragged all-gather,
-// 1 = the copy plan, 2 / 3 = the fused fp8 two-shot, wide / narrow (dtype = the output dtype).
+// 1 = the copy plan, 2 / 3 = the fused fp8 two-shot, wide / narrow (dtype = the output dtype),
+// 4 / 5 = the fp8 reduce-scatter / all-gather halves.
 int mp4x_ipc_occupancy_ar(int algo, int dtype, int op, int p, int* blocks_per_cu);
 int mp4x_ipc_occupancy_push(int dtype, int op, int p, int* blocks_per_cu);
 int mp4x_ipc_occupancy_rs(int dtype, int op, int p, int* blocks_per_cu);

@@ -121,10 +121,12 @@ __device__ __forceinline__ float group16_max(float v) {
 // storing straight from registers would leave every store instruction 16 bytes per line.  The
 // values go through a wave-private LDS tile (20-float lane pitch: 16-byte aligned, spread over
 // the banks) and leave as 16-byte-per-lane CONTIGUOUS stores (1 KB of f32 per instruction).
+// LO (the reduce-scatter half): only 4-element groups at or after element `lo` are stored, so a
+// quant block shared with the previous rank's segment is written inside the own segment only.
 constexpr int kFp8LdsPitch = 20;
-template <int DT>
+template <int DT, bool LO = false>
 __device__ __forceinline__ void fp8_wave_store(float* tile, const float (&y)[16], int lane, void* out,
-                                               int64_t b0, int64_t cb_end, int64_t n) {
+                                               int64_t b0, int64_t cb_end, int64_t n, int64_t lo = 0) {
 #pragma unroll
   for (int d = 0; d < 4; ++d)
     *reinterpret_cast<float4*>(tile + lane * kFp8LdsPitch + d * 4) = make_float4(y[4 * d], y[4 * d + 1],
@@ -136,7 +138,9 @@ __device__ __forceinline__ void fp8_wave_store(float* tile, const float (&y)[16]
     const int e = (d * 64 + lane) * 4;                  // value index inside the wave's 1024
     const float4 v = *reinterpret_cast<const float4*>(tile + (e >> 4) * kFp8LdsPitch + (e & 15));
     const int64_t blk = b0 + (e >> 8);
-    if (blk < cb_end) {
+    bool in = blk < cb_end;
+    if constexpr (LO) in = in && b0 * kQBlock + e >= lo;
+    if (in) {
       float x[4] = {v.x, v.y, v.z, v.w};
       store4<DT>(out, b0 * kQBlock + e, n, x);
     }
@@ -239,6 +243,128 @@ __global__ __launch_bounds__(kIpcThreads) void k_ipc_fp8_twoshot(IpcPtrs P, Sign
         y[4 * d] = yy[0]; y[4 * d + 1] = yy[1]; y[4 * d + 2] = yy[2]; y[4 * d + 3] = yy[3];
       }
       fp8_wave_store<DT>(tile, y, lane, out, (int64_t)k * cb + t * 4, (int64_t)k * cb + cb, n);
+    }
+  }
+  block_barrier(P, 2, rank, p, epoch, self);
+}
+
+// ---------------------------------------------------------------- the two halves as collectives
+// reduceScatterArray / allgatherArray with the fp8 operand: the halves of the two-shot over RAGGED
+// per-rank segments, each a kernel of its own with the wide layout above (16 bytes per lane per
+// peer, four quant blocks per wave step, every peer's load issued before the first FMA, stores
+// through the wave's LDS tile) and a start and an end barrier.  The quantise of this rank's data
+// into its own buffer runs just before, stream-ordered, as in the allreduce.
+//
+// Reduce-scatter: every rank quantised the WHOLE range of the piece on one block grid counted
+// from the piece's first element (q bytes at 0, f32 scales at `soff`, `nblk` blocks).  This rank
+// reduces the blocks [blo, bhi) that touch its segment [elo, ehi) (elements from the piece start,
+// multiples of 4), sums them in rank order in f32 and stores with ONE rounding, in place, only the
+// 4-element groups inside its segment: a block that straddles two segments is reduced by both
+// ranks and written by each inside its own.  Nothing is re-quantised.  Every rank launches the
+// same grid (sized from the largest block count of any rank), also for an empty segment.
+template <int DT, int NR>
+__global__ __launch_bounds__(kIpcThreads) void k_ipc_fp8_rs(IpcPtrs P, Signal* self, int rank, int64_t blo,
+                                                             int64_t bhi, int64_t nblk, int64_t soff,
+                                                             void* __restrict__ out, int64_t elo, int64_t ehi,
+                                                             uint32_t epoch, const uint32_t* epoch_dev) {
+  constexpr int p = NR;
+  MP4X_DASSERT(rank >= 0 && rank < NR && blockIdx.x < kIpcMaxBlocks);
+  MP4X_DASSERT(blo >= 0 && blo <= bhi && bhi <= nblk && soff >= nblk * kQBlock);
+  MP4X_DASSERT(elo <= ehi && (elo == ehi || (elo >= blo * kQBlock && ehi <= bhi * kQBlock)));
+  (void)nblk;
+  __shared__ __attribute__((aligned(16))) float s_tile[kIpcThreads * kFp8LdsPitch];
+  epoch = resolve_epoch(epoch, epoch_dev);
+  if (!block_barrier(P, 0, rank, p, epoch, self)) return;
+  const int lane = threadIdx.x & 63;
+  const int g = lane >> 4;                 // quant block of this lane within the wave's 4
+  const int sub = lane & 15;               // 16-byte slot inside the 256-byte block
+  constexpr int kWaves = kIpcThreads / 64;
+  float* tile = s_tile + (threadIdx.x >> 6) * 64 * kFp8LdsPitch;
+  const int64_t w0 = (int64_t)blockIdx.x * kWaves + (threadIdx.x >> 6);
+  const int64_t nw = (int64_t)gridDim.x * kWaves;
+  const int64_t nquad = (bhi - blo + 3) / 4;             // wave steps over the own blocks
+  for (int64_t t = w0; t < nquad; t += nw) {
+    const int64_t j = blo + t * 4 + g;                   // quant block on the piece's grid
+    const bool live = j < bhi;
+    const int64_t b = live ? j : blo;
+    MP4X_DASSERT(b >= 0 && b < nblk);
+    u32x4 w[NR];
+    float sc[NR];
+#pragma unroll
+    for (int k = 0; k < NR; ++k) {                        // every peer's 16 bytes in flight at once
+      const u32x4* q = reinterpret_cast<const u32x4*>(P.data[k]);
+      w[k] = live ? q[b * 16 + sub] : u32x4{0u, 0u, 0u, 0u};
+      sc[k] = live ? reinterpret_cast<const float*>(reinterpret_cast<const char*>(q) + soff)[b] : 0.0f;
+    }
+    float y[16];
+#pragma unroll
+    for (int d = 0; d < 4; ++d) {
+      float acc[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+#pragma unroll
+      for (int k = 0; k < NR; ++k) fp8_fma_acc(w[k][d], sc[k], acc);   // rank order: deterministic
+      y[4 * d] = acc[0]; y[4 * d + 1] = acc[1]; y[4 * d + 2] = acc[2]; y[4 * d + 3] = acc[3];
+    }
+    fp8_wave_store<DT, true>(tile, y, lane, out, blo + t * 4, bhi, ehi, elo);
+  }
+  block_barrier(P, 2, rank, p, epoch, self);
+}
+
+// All-gather: rank k quantised ITS segment of the piece on a block grid counted from the segment's
+// start; its buffer holds only that (q bytes at 0, scales at `soff`, which comes from the largest
+// segment).  Every rank pulls the blocks of every segment — its own included, from its own
+// buffer, so all ranks end up with the same bytes — and dequantises them straight into
+// out[S.lo[k], S.hi[k]) (elements of the output; S.lo 16-byte aligned offsets).
+template <int DT, int NR>
+__global__ __launch_bounds__(kIpcThreads) void k_ipc_fp8_ag(IpcPtrs P, Signal* self, int rank, Segs S,
+                                                             int64_t maxblk, int64_t soff, void* __restrict__ out,
+                                                             uint32_t epoch, const uint32_t* epoch_dev) {
+  constexpr int p = NR;
+  using ST = typename Elem<DT>::S;
+  MP4X_DASSERT(rank >= 0 && rank < NR && blockIdx.x < kIpcMaxBlocks);
+  MP4X_DASSERT(maxblk >= 0 && soff >= maxblk * kQBlock);
+  __shared__ __attribute__((aligned(16))) float s_tile[kIpcThreads * kFp8LdsPitch];
+  epoch = resolve_epoch(epoch, epoch_dev);
+  if (!block_barrier(P, 0, rank, p, epoch, self)) return;
+  const int lane = threadIdx.x & 63;
+  const int g = lane >> 4;
+  const int sub = lane & 15;
+  constexpr int kWaves = kIpcThreads / 64;
+  float* tile = s_tile + (threadIdx.x >> 6) * 64 * kFp8LdsPitch;
+  const int64_t w0 = (int64_t)blockIdx.x * kWaves + (threadIdx.x >> 6);
+  const int64_t nw = (int64_t)gridDim.x * kWaves;
+  const int64_t nquad = (maxblk + 3) / 4;                // wave steps over the largest segment
+  int64_t nb[NR];
+#pragma unroll
+  for (int k = 0; k < NR; ++k) {
+    MP4X_DASSERT(S.lo[k] >= 0 && S.lo[k] <= S.hi[k]);
+    nb[k] = (S.hi[k] - S.lo[k] + kQBlock - 1) / kQBlock;  // quant blocks of segment k
+    MP4X_DASSERT(nb[k] <= maxblk);
+  }
+  for (int64_t t = w0; t < nquad; t += nw) {
+    const int64_t j = t * 4 + g;                         // segment-relative quant block
+    u32x4 w[NR];
+    float sc[NR];
+#pragma unroll
+    for (int k = 0; k < NR; ++k) {                        // every peer's 16 bytes in flight at once
+      const u32x4* q = reinterpret_cast<const u32x4*>(P.data[k]);
+      const bool live = j < nb[k];
+      const int64_t b = live ? j : 0;
+      w[k] = live ? q[b * 16 + sub] : u32x4{0u, 0u, 0u, 0u};
+      sc[k] = live ? reinterpret_cast<const float*>(reinterpret_cast<const char*>(q) + soff)[b] : 0.0f;
+    }
+#pragma unroll
+    for (int k = 0; k < NR; ++k) {
+      if (t * 4 >= nb[k]) continue;                       // wave-uniform: segment k ends before this step
+      float y[16];
+#pragma unroll
+      for (int d = 0; d < 4; ++d) {
+        // the codec's one-input dequant-reduce, fma(code, scale, +0): what the reduce-scatter half
+        // gives for p = 1 (a -0 code decodes to +0, where unpack_fp8's product would keep the sign)
+        float yy[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+        fp8_fma_acc(w[k][d], sc[k], yy);
+        y[4 * d] = yy[0]; y[4 * d + 1] = yy[1]; y[4 * d + 2] = yy[2]; y[4 * d + 3] = yy[3];
+      }
+      fp8_wave_store<DT>(tile, y, lane, reinterpret_cast<ST*>(out) + S.lo[k], t * 4, nb[k], S.hi[k] - S.lo[k]);
     }
   }
   block_barrier(P, 2, rank, p, epoch, self);
@@ -488,6 +614,120 @@ extern "C" int mp4x_ipc_fp8_allreduce(int dtype, void* const* data_ptrs, void* c
   }
 }
 
+// Grid of the fp8 halves when the caller passes none: one wave per 4 quant blocks of the LARGEST
+// share of any rank (rank-independent), 8 waves per block.
+static int fp8_half_blocks(int blocks, int64_t maxblk) {
+  if (blocks <= 0) {
+    const int64_t waves = (maxblk + 3) / 4;
+    const int64_t b = (waves + kIpcThreads / 64 - 1) / (kIpcThreads / 64);
+    blocks = (int)(b < 1 ? 1 : b);
+  }
+  return blocks > kIpcMaxBlocks ? kIpcMaxBlocks : blocks;
+}
+
+static int fp8_half_common_check(int dtype, int rank, int p, int64_t nblk, int64_t soff, const int64_t* seg_lo,
+                                 const int64_t* seg_hi, const void* out) {
+  if (dtype != MP4X_F32 && dtype != MP4X_BF16 && dtype != MP4X_F16) return MP4X_E_UNSUPPORTED;
+  if (p < 2 || p > kIpcMaxRanks || rank < 0 || rank >= p) return MP4X_E_BADARG;
+  if (nblk <= 0 || (soff & 15) || soff < nblk * kQBlock) return MP4X_E_BADARG;     // scales after the q bytes
+  if (!out || ((uintptr_t)out & 15) || !seg_lo || !seg_hi) return MP4X_E_BADARG;
+  return 0;
+}
+
+// The block range [*blo, *bhi) of segment [lo, hi) on a 256-element grid (empty for an empty segment).
+static void fp8_seg_blocks(int64_t lo, int64_t hi, int64_t* blo, int64_t* bhi) {
+  *blo = lo / kQBlock;
+  *bhi = hi > lo ? (hi + kQBlock - 1) / kQBlock : *blo;
+}
+
+extern "C" int mp4x_ipc_fp8_reduce_scatter_check(int dtype, int rank, int p, int64_t nblk, int64_t soff,
+                                                 const int64_t* seg_lo, const int64_t* seg_hi, const void* out) {
+  if (int e = fp8_half_common_check(dtype, rank, p, nblk, soff, seg_lo, seg_hi, out)) return e;
+  int64_t prev = 0;
+  for (int k = 0; k < p; ++k) {        // ascending, inside the quantised blocks, whole 4-element groups
+    if (seg_lo[k] < prev || seg_hi[k] < seg_lo[k] || seg_hi[k] > nblk * kQBlock) return MP4X_E_BADARG;
+    if ((seg_lo[k] | seg_hi[k]) & 3) return MP4X_E_BADARG;
+    prev = seg_hi[k];
+  }
+  return 0;
+}
+
+extern "C" int mp4x_ipc_fp8_reduce_scatter(int dtype, void* const* data_ptrs, void* const* signal_ptrs, int rank,
+                                           int p, int64_t nblk, int64_t soff, const int64_t* seg_lo,
+                                           const int64_t* seg_hi, void* out, uint32_t epoch, int blocks,
+                                           const uint32_t* epoch_dev, void* stream) {
+  if (int e = mp4x_ipc_fp8_reduce_scatter_check(dtype, rank, p, nblk, soff, seg_lo, seg_hi, out)) return e;
+  IpcPtrs P;
+  if (int e = ipc_prepare(data_ptrs, signal_ptrs, rank, p, &P)) return e;
+  int64_t maxblk = 0, blo = 0, bhi = 0;
+  for (int k = 0; k < p; ++k) {
+    int64_t a, b;
+    fp8_seg_blocks(seg_lo[k], seg_hi[k], &a, &b);
+    if (b - a > maxblk) maxblk = b - a;
+    if (k == rank) { blo = a; bhi = b; }
+  }
+  blocks = fp8_half_blocks(blocks, maxblk);
+  const int64_t elo = seg_lo[rank], ehi = seg_hi[rank];
+  Signal* self = (Signal*)signal_ptrs[rank];
+  hipStream_t st = (hipStream_t)stream;
+  return with_nr(p, [&](auto nrc) {
+    constexpr int NR = decltype(nrc)::value;
+#define MP4X_FP8RS_CASE(DT)                                                                                    \
+  case DT:                                                                                                     \
+    hipLaunchKernelGGL((k_ipc_fp8_rs<DT, NR>), dim3(blocks), dim3(kIpcThreads), 0, st, P, self, rank, blo, bhi, \
+                       nblk, soff, out, elo, ehi, epoch, epoch_dev);                                           \
+    return (int)hipGetLastError();
+    switch (dtype) {
+      MP4X_FP8RS_CASE(MP4X_F32) MP4X_FP8RS_CASE(MP4X_BF16) MP4X_FP8RS_CASE(MP4X_F16)
+      default: return (int)MP4X_E_UNSUPPORTED;
+    }
+#undef MP4X_FP8RS_CASE
+  });
+}
+
+extern "C" int mp4x_ipc_fp8_allgather_check(int dtype, int rank, int p, int64_t maxblk, int64_t soff,
+                                            const int64_t* seg_lo, const int64_t* seg_hi, const void* out) {
+  if (int e = fp8_half_common_check(dtype, rank, p, maxblk, soff, seg_lo, seg_hi, out)) return e;
+  for (int k = 0; k < p; ++k) {        // not descending, no longer than the quantised blocks, 4-element groups
+    if (seg_lo[k] < 0 || seg_hi[k] < seg_lo[k] || seg_hi[k] - seg_lo[k] > maxblk * kQBlock) return MP4X_E_BADARG;
+    if ((seg_lo[k] | seg_hi[k]) & 3) return MP4X_E_BADARG;
+  }
+  return 0;
+}
+
+extern "C" int mp4x_ipc_fp8_allgather(int dtype, void* const* data_ptrs, void* const* signal_ptrs, int rank, int p,
+                                      int64_t maxblk, int64_t soff, const int64_t* seg_lo, const int64_t* seg_hi,
+                                      void* out, uint32_t epoch, int blocks, const uint32_t* epoch_dev,
+                                      void* stream) {
+  if (int e = mp4x_ipc_fp8_allgather_check(dtype, rank, p, maxblk, soff, seg_lo, seg_hi, out)) return e;
+  IpcPtrs P;
+  if (int e = ipc_prepare(data_ptrs, signal_ptrs, rank, p, &P)) return e;
+  Segs S;
+  int64_t used = 0;
+  for (int k = 0; k < kIpcMaxRanks; ++k) {
+    S.lo[k] = k < p ? seg_lo[k] : 0;
+    S.hi[k] = k < p ? seg_hi[k] : 0;
+    const int64_t nb = (S.hi[k] - S.lo[k] + kQBlock - 1) / kQBlock;
+    if (nb > used) used = nb;
+  }
+  blocks = fp8_half_blocks(blocks, used);
+  Signal* self = (Signal*)signal_ptrs[rank];
+  hipStream_t st = (hipStream_t)stream;
+  return with_nr(p, [&](auto nrc) {
+    constexpr int NR = decltype(nrc)::value;
+#define MP4X_FP8AG_CASE(DT)                                                                                   \
+  case DT:                                                                                                    \
+    hipLaunchKernelGGL((k_ipc_fp8_ag<DT, NR>), dim3(blocks), dim3(kIpcThreads), 0, st, P, self, rank, S, used, \
+                       soff, out, epoch, epoch_dev);                                                          \
+    return (int)hipGetLastError();
+    switch (dtype) {
+      MP4X_FP8AG_CASE(MP4X_F32) MP4X_FP8AG_CASE(MP4X_BF16) MP4X_FP8AG_CASE(MP4X_F16)
+      default: return (int)MP4X_E_UNSUPPORTED;
+    }
+#undef MP4X_FP8AG_CASE
+  });
+}
+
 extern "C" int mp4x_memset_async(void* dst, int value, size_t bytes, void* stream) {
   return (int)hipMemsetAsync(dst, value, bytes, (hipStream_t)stream);
 }
@@ -546,6 +786,17 @@ extern "C" int mp4x_ipc_occupancy_misc(int family, int dtype, int p, int* blocks
       if (family == 0) {
         occ_min(k_ipc_gather<NR>, &m);
         return 0;
+      }
+      if (family == 4 || family == 5) {                  // the fp8 halves as collectives
+        switch (dtype) {
+          case MP4X_F32: family == 4 ? occ_min(k_ipc_fp8_rs<MP4X_F32, NR>, &m)
+                                     : occ_min(k_ipc_fp8_ag<MP4X_F32, NR>, &m); return 0;
+          case MP4X_BF16: family == 4 ? occ_min(k_ipc_fp8_rs<MP4X_BF16, NR>, &m)
+                                      : occ_min(k_ipc_fp8_ag<MP4X_BF16, NR>, &m); return 0;
+          case MP4X_F16: family == 4 ? occ_min(k_ipc_fp8_rs<MP4X_F16, NR>, &m)
+                                     : occ_min(k_ipc_fp8_ag<MP4X_F16, NR>, &m); return 0;
+          default: return (int)MP4X_E_UNSUPPORTED;
+        }
       }
       const bool narrow = family == 3;
       switch (dtype) {

@@ -53,10 +53,12 @@ class _Bucket:
     slice's master copy, and the backward-hook bookkeeping."""
 
     def __init__(self, params: List[torch.nn.Parameter], p: int, r: int, param_arena: torch.Tensor,
-                 grad_arena: torch.Tensor, off: int, master_dtype: torch.dtype):
+                 grad_arena: torch.Tensor, off: int, master_dtype: torch.dtype, grad_codec: Optional[str] = None):
         dt = params[0].dtype
         self.params = params
         self.operand: Operand = _OPERAND[dt]()
+        # the gradient reduce-scatter's operand: the bucket's own, or one that carries the wire codec
+        self.grad_operand: Operand = _OPERAND[dt](codec=grad_codec) if grad_codec else self.operand
         self.op = for_dtype(Operators.Float.SUM, dtype_of_torch(dt))
         self.n = _padded(params, p)
         self.shard = self.n // p
@@ -86,12 +88,17 @@ class ZeroOptimizer:
     lr=1e-3)``; per step: ``zero_grad()``, forward/backward, ``step()``.  All ranks must build it
     with the same parameter list (the constructor is collective when it allocates memAlloc
     arenas).  ``bucket_mb``: reduce-scatter granularity (default ``MP4X_BUCKET_MB`` = 64);
-    ``overlap``: launch each bucket's reduce-scatter from the backward hooks (default: on GPUs)."""
+    ``overlap``: launch each bucket's reduce-scatter from the backward hooks (default: on GPUs);
+    ``grad_codec``: ``"fp8"`` sends the gradients of the reduce-scatter as block-scaled e4m3 (a
+    quarter of the f32 bytes on every link, quantised ONCE — the compressed allreduce of
+    ``models/ddp.py`` quantises twice); the parameter all-gather stays exact.  Strictly opt-in, for
+    f32 / bf16 / f16 parameters (``ValueError`` for f64); where the compressed form does not
+    apply (no GPU mesh, ``MP4X_FP8_TRANSPORT=rccl``) the reduce-scatter is the exact one."""
 
     def __init__(self, comm, params: Iterable[torch.nn.Parameter], optimizer=torch.optim.AdamW,
                  average: bool = True, max_grad_norm: Optional[float] = None,
                  master_dtype: torch.dtype = torch.float32, bucket_mb: Optional[float] = None,
-                 overlap: Optional[bool] = None, **optim_kwargs):
+                 overlap: Optional[bool] = None, grad_codec: Optional[str] = None, **optim_kwargs):
         self.comm = comm
         self.p, self.r = comm.getSlaveNum(), comm.getRank()
         self.average = average
@@ -102,6 +109,11 @@ class ZeroOptimizer:
         for q in params:
             if q.dtype not in _OPERAND:
                 raise ValueError(f"ZeroOptimizer: unsupported parameter dtype {q.dtype}")
+        if grad_codec not in (None, "fp8"):
+            raise ValueError(f"ZeroOptimizer: unknown grad_codec {grad_codec!r} (None or 'fp8')")
+        if grad_codec and any(q.dtype == torch.float64 for q in params):
+            raise ValueError("ZeroOptimizer: grad_codec needs f32 / bf16 / f16 parameters (got float64)")
+        self.grad_codec = grad_codec
         cap = int((bucket_mb or float(os.environ.get("MP4X_BUCKET_MB", 64))) * (1 << 20))
         runs: Dict[torch.dtype, List[List[torch.nn.Parameter]]] = {}
         for q in reversed(params):                       # backward order; identical on every rank
@@ -125,7 +137,7 @@ class ZeroOptimizer:
             self._arenas += [pa, ga]
             off = 0
             for b in rs:
-                self.buckets.append(_Bucket(b, self.p, self.r, pa, ga, off, master_dtype))
+                self.buckets.append(_Bucket(b, self.p, self.r, pa, ga, off, master_dtype, grad_codec))
                 off += self.buckets[-1].n
         self._owner = {}
         self._hooks = []
@@ -155,9 +167,9 @@ class ZeroOptimizer:
             ev.record()                                  # the bucket's gradients are complete here
             with torch.cuda.stream(self.stream):
                 self.stream.wait_event(ev)
-                self.comm.reduceScatterArray(b.grad, b.operand, b.op, 0, [b.shard] * self.p)
+                self.comm.reduceScatterArray(b.grad, b.grad_operand, b.op, 0, [b.shard] * self.p)
         else:
-            self.comm.reduceScatterArray(b.grad, b.operand, b.op, 0, [b.shard] * self.p)
+            self.comm.reduceScatterArray(b.grad, b.grad_operand, b.op, 0, [b.shard] * self.p)
 
     @contextlib.contextmanager
     def no_sync(self):
@@ -272,7 +284,8 @@ class ZeroOptimizer:
 
 def train_zero(comm, steps: int = 5, global_batch: int = 64, din: int = 64, hidden: int = 128, dout: int = 16,
                lr: float = 0.01, device="cpu", dtype=torch.float32, max_grad_norm=None,
-               bucket_mb: Optional[float] = None, overlap: Optional[bool] = None, micro: int = 1) -> List[float]:
+               bucket_mb: Optional[float] = None, overlap: Optional[bool] = None, micro: int = 1,
+               grad_codec: Optional[str] = None) -> List[float]:
     """The MLP of :mod:`mp4x.models.mlp` trained data-parallel with AdamW under ZeroOptimizer
     (``micro`` gradient-accumulation micro-batches per step); returns the GLOBAL loss per step."""
     from .mlp import MLP, synthetic_batch
@@ -280,7 +293,7 @@ def train_zero(comm, steps: int = 5, global_batch: int = 64, din: int = 64, hidd
     torch.manual_seed(0)
     model = MLP(din, hidden, dout).to(device=device, dtype=dtype)
     opt = ZeroOptimizer(comm, model.parameters(), torch.optim.AdamW, lr=lr, weight_decay=0.01,
-                        max_grad_norm=max_grad_norm, bucket_mb=bucket_mb, overlap=overlap)
+                        max_grad_norm=max_grad_norm, bucket_mb=bucket_mb, overlap=overlap, grad_codec=grad_codec)
     losses = []
     shard = global_batch // p
     mb = shard // micro

@@ -16,7 +16,10 @@ Algorithm families (selected per call, see :meth:`DeviceEngine.select`):
            bitwise / *_LOC / int16) → all-gather.  Reduce-scatter alone is the first half.
 ``fp8``    the same two-shot schedule with the K6 block-scaled e4m3 codec on the wire:
            quantise → all-to-all(q, scales) → fused dequant+reduce(f32)+requant →
-           all-gather(q, scales) → dequant.  4x fewer bytes than f32 on every link.
+           all-gather(q, scales) → dequant.  4x fewer bytes than f32 on every link.  With an
+           IPC mesh the fp8 operand is honoured by reduce_scatter (SUM) and allgather too: the
+           halves as kernels of their own (counted ``reduce_scatter.fp8.ipc`` /
+           ``allgather.fp8.ipc``; opt-in through the operand only, never tuned).
 ``p2p``    grouped ncclSend/ncclRecv (batch_isend_irecv) for gather / scatter /
            ragged allgather: the root talks to all peers concurrently.
 ``ipc*``   mp4x's own xGMI kernels over IPC-mapped peer memory (parallel/ipc.py,
@@ -1376,6 +1379,17 @@ class DeviceEngine(AutotuneMixin, ScheduleMixin, RootedMixin):
                 inst.allreduce_fp8(t)
                 tol = 0.25 * float(exp.abs().max())
                 check("fp8_twoshot", lambda: ((t - exp).abs() > tol).sum())
+                # the two halves as collectives, once each, within the same bound
+                froms, tos, _ = CommUtils.even_split(0, n, p)
+                mine = slice(froms[r], tos[r])
+                exp = self._fill_probe(t, op, salt=7)
+                inst.reduce_scatter_fp8(t, froms, tos)
+                tol = 0.25 * float(exp.abs().max())
+                check("fp8_reduce_scatter", lambda: ((t[mine] - exp[mine]).abs() > tol).sum())
+                t.fill_(-1)
+                t[mine] = exp[mine]
+                inst.allgather_fp8(t, froms, tos)
+                check("fp8_allgather", lambda: ((t - exp).abs() > tol).sum())
             del t
             inst.set_spin(ipcm.spin_default())
         except Exception as e:   # noqa: BLE001
@@ -1401,9 +1415,14 @@ class DeviceEngine(AutotuneMixin, ScheduleMixin, RootedMixin):
             return arr
         op = self._op(operator, whole)
         counts = [t - f for f, t in zip(froms, tos)]
+        if getattr(operand, "codec", None) == "fp8":
+            memo = None     # the exact forms below must not be memoised under a key that carries the codec
+            if not getattr(op, "is_custom", False) and op.code == OpCode.SUM:
+                inst = self._fp8_half_inst(flat, froms, tos)
+                if inst is not None and inst.reduce_scatter_fp8(flat, froms, tos):
+                    self._count("reduce_scatter.fp8.ipc")      # e4m3 on the links, quantised once
+                    return arr
         algo = self.select("reduce_scatter", whole.numel() * whole.element_size(), op, whole.dtype, operand)
-        if algo == "fp8":
-            algo = "a2a"    # exact path for ragged RS; fp8 RS is used inside the compressed allreduce
         if algo in ("rccl", "a2a") and self._zc_ok(whole) and self._ipc_obj.reduce_scatter_registered(flat, froms,
                                                                                                         tos, op):
             self._count("reduce_scatter.ipc_zc")       # registered tensor: zero copy, any size
@@ -1441,9 +1460,25 @@ class DeviceEngine(AutotuneMixin, ScheduleMixin, RootedMixin):
         return arr
 
     # ================================================================== allgather
-    def allgather(self, arr: torch.Tensor, froms, tos, memo: bool = False):
+    def _fp8_half_inst(self, flat: torch.Tensor, froms, tos):
+        """The IPC instance that runs the fp8 reduce-scatter / all-gather of this range, or None
+        (the exact forms): :meth:`_ipc_fp8`'s rule, with ``need`` counted from the whole range —
+        no mesh, ``MP4X_FP8_TRANSPORT=rccl``, a capture with no device epoch, a host tensor or
+        offsets off the 16-byte grid keep the exact path (rank-independent facts only)."""
+        from .ipc import IpcAllreduce
+        if not flat.is_cuda or not IpcAllreduce.fp8_range_ok(flat, froms, tos):
+            return None
+        return self._ipc_fp8(flat[froms[0]:tos[-1]])
+
+    def allgather(self, arr: torch.Tensor, froms, tos, memo: bool = False, operand=None):
         flat = self._flat(arr)
         whole = flat[froms[0]:tos[-1]]
+        if getattr(operand, "codec", None) == "fp8":
+            memo = False    # the fast path's key carries no codec: never memoise a call made with it
+            inst = self._fp8_half_inst(flat, froms, tos) if whole.numel() else None
+            if inst is not None and inst.allgather_fp8(flat, froms, tos):
+                self._count("allgather.fp8.ipc")           # e4m3 on the links
+                return arr
         if whole.numel() and self._zc_ok(whole) and self._ipc_obj.allgather_registered(flat, froms, tos):
             self._count("allgather.ipc_zc")            # registered tensor: zero copy, any size
             return arr

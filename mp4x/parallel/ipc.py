@@ -487,7 +487,7 @@ class IpcAllreduce(IpcForms):
             self.set_spin(old)
 
     # ---------------------------------------------------------------- co-residency grid caps
-    _OCC_FAMILY = {"gather": 0, "plan": 1, "fp8": 2, "fp8n": 3}
+    _OCC_FAMILY = {"gather": 0, "plan": 1, "fp8": 2, "fp8n": 3, "fp8rs": 4, "fp8ag": 5}
 
     def grid_cap(self, family: str, dtype=None, op=None) -> int:
         """Largest grid a launch of ``family`` ((dtype, op) kernel; see parallel/occupancy.py)
@@ -1302,13 +1302,139 @@ class IpcAllreduce(IpcForms):
             off += m
         return view
 
-    def _blocks_for_waves(self, waves: int, dtype) -> int:
-        """Grid of the fused fp8 two-shot (8 waves per block).  On a GPU shared by the ranks
-        (rehearsals) the cap of this kernel's occupancy applies (:meth:`grid_cap`; its 40 KB LDS
-        tile and register load fit fewer blocks per CU than the generic kernels)."""
+    # ---------------------------------------------------------------- the fp8 halves as collectives
+    # reduceScatterArray / allgatherArray with the fp8 operand (csrc/runtime/ipc.hip k_ipc_fp8_rs /
+    # k_ipc_fp8_ag).  Per piece: quantise into the own buffer (K6), then ONE kernel with a start and
+    # an end barrier.  The reduce-scatter quantises once where the allreduce quantises twice.
+    @classmethod
+    def fp8_range_ok(cls, view: torch.Tensor, froms, tos) -> bool:
+        """Rank-independent qualification of the fp8 reduce-scatter / all-gather: a contiguous
+        f32 / bf16 / f16 tensor, a non-empty range, and every offset a 16-byte multiple from the
+        range start (:meth:`_range_ok`'s grid; the size is free, larger ranges run in pieces).  The
+        tensor's own address is not part of it (see :meth:`reduce_scatter_fp8`)."""
+        es = view.element_size()
+        base = froms[0]
+        return view.dtype in cls.FP8_DTYPES and view.is_contiguous() and tos[-1] > base and \
+            all(((f - base) * es) % 16 == 0 and ((t - base) * es) % 16 == 0 and t >= f for f, t in zip(froms, tos))
+
+    def _fp8_half_blocks(self) -> int:
+        """Quant blocks per piece of the fp8 halves: 256 code bytes + a 4-byte scale each (scales
+        16-byte aligned after the codes)."""
+        b = (self.nbytes - 16) // (self.QBLOCK + 4)
+        if b < 1:
+            raise Mp4jException("IPC buffer too small for the fp8 reduce-scatter / all-gather")
+        return int(b)
+
+    def _fp8_stage(self, dt: int, src: int, n: int, nblk: int, soff: int, st) -> None:
+        """Quantise ``n`` elements at ``src`` into the own buffer on an ``nblk``-block layout (codes
+        at 0, scales at ``soff``); the blocks past the input are zeroed, as in the allreduce."""
+        own = self._data.value
+        used = -(-n // self.QBLOCK)
+        if used < nblk:
+            check(self.lib.mp4x_memset_async(own + used * self.QBLOCK, 0, (nblk - used) * self.QBLOCK, st), "fp8 q tail")
+            check(self.lib.mp4x_memset_async(own + soff + used * 4, 0, (nblk - used) * 4, st), "fp8 scale tail")
+        if n:
+            check(self.lib.mp4x_quant_fp8(dt, src, n, own, own + soff, st), "fp8 quant")
+
+    def reduce_scatter_fp8(self, view: torch.Tensor, froms, tos) -> bool:
+        """In place SUM reduce-scatter with the block-scaled e4m3 codec on the links:
+        ``view[froms[r]:tos[r]]`` <- the f32 sum, in rank order, of every rank's quantised range,
+        stored with one rounding; nothing else is written.  The range ``[froms[0], tos[-1])`` is
+        quantised on ONE block grid counted from its start, and pieces (a range whose codes exceed
+        the buffer) are cut on that grid, so the result does not depend on the buffer size.  Every
+        rank runs the same pieces with the same grid, also where its own share is empty.  Returns
+        False (nothing done) when the call does not qualify (:meth:`fp8_range_ok`)."""
+        if not self.fp8_range_ok(view, froms, tos):
+            return False
+        flat = view.view(-1)
+        base, end, r = froms[0], tos[-1], self.rank
+        rng = flat[base:end]
+        if rng.data_ptr() % 16:
+            # an oddly offset range on THIS rank: the same kernels on an aligned temporary
+            tmp = torch.empty_like(rng)
+            tmp.copy_(rng)
+            rel_f, rel_t = [f - base for f in froms], [t - base for t in tos]
+            self.reduce_scatter_fp8(tmp, rel_f, rel_t)
+            if rel_t[r] > rel_f[r]:
+                rng[rel_f[r]:rel_t[r]].copy_(tmp[rel_f[r]:rel_t[r]])
+            return True
+        Q = self.QBLOCK
+        n = end - base
+        es = view.element_size()
+        dt = int(dtype_of_torch(view.dtype))
+        cap = self._fp8_half_blocks()
+        nblk_all = -(-n // Q)
+        for b0 in range(0, nblk_all, cap):
+            nblk = min(cap, nblk_all - b0)
+            e0 = b0 * Q                                   # the piece's first element, from the range start
+            m = min(n - e0, nblk * Q)
+            soff = (nblk * Q + 15) // 16 * 16
+            lo = [min(max(f - base - e0, 0), m) for f in froms]
+            hi = [min(max(t - base - e0, 0), m) for t in tos]
+            maxblk = max((-(-h // Q) - l_ // Q) if h > l_ else 0 for l_, h in zip(lo, hi))
+            lo_a, hi_a = (ctypes.c_int64 * self.p)(*lo), (ctypes.c_int64 * self.p)(*hi)
+            src = rng.data_ptr() + e0 * es
+            self.raise_if_failed()
+            st = self._launch_stream()
+            # every refusal BEFORE the epoch moves: a refused piece leaves this rank's epoch in step
+            check(self.lib.mp4x_ipc_fp8_reduce_scatter_check(dt, r, self.p, nblk, soff, lo_a, hi_a, src),
+                  "mp4x_ipc_fp8_reduce_scatter")
+            self._fp8_stage(dt, src, m, nblk, soff, st)
+            edev = self._next_epoch(st)
+            check(self.lib.mp4x_ipc_fp8_reduce_scatter(dt, self._pp_data[0], self._pp_sig[0], r, self.p, nblk, soff,
+                                                       lo_a, hi_a, src, self.epoch,
+                                                       self._blocks_for_waves(-(-maxblk // 4), view.dtype, "fp8rs"),
+                                                       edev, st), "mp4x_ipc_fp8_reduce_scatter")
+        return True
+
+    def allgather_fp8(self, view: torch.Tensor, froms, tos) -> bool:
+        """In place all-gather with the block-scaled e4m3 codec on the links: every rank's
+        ``view[froms[k]:tos[k]]`` is quantised by its owner on a block grid counted from the
+        segment's start and lands everywhere dequantised — on its owner too, so all ranks hold the
+        same bytes.  Pieces are cut on each segment's own grid (the result does not depend on the
+        buffer size); every rank runs the same number of pieces.  Returns False (nothing done)
+        when the call does not qualify (:meth:`fp8_range_ok`)."""
+        if not self.fp8_range_ok(view, froms, tos):
+            return False
+        flat = view.view(-1)
+        base, end, r = froms[0], tos[-1], self.rank
+        rng = flat[base:end]
+        if rng.data_ptr() % 16:
+            return self._aligned(rng, lambda t: self.allgather_fp8(t, [f - base for f in froms],
+                                                                   [t_ - base for t_ in tos]))
+        Q = self.QBLOCK
+        es = view.element_size()
+        dt = int(dtype_of_torch(view.dtype))
+        cap = self._fp8_half_blocks()
+        lens = [t - f for f, t in zip(froms, tos)]
+        out = rng.data_ptr()
+        for b0 in range(0, -(-max(lens) // Q), cap):
+            e0 = b0 * Q                                   # the piece's first element, from each segment's start
+            plen = [min(max(ln - e0, 0), cap * Q) for ln in lens]
+            maxblk = -(-max(plen) // Q)
+            soff = (maxblk * Q + 15) // 16 * 16
+            lo = [f - base + min(e0, ln) for f, ln in zip(froms, lens)]
+            hi = [l_ + pl for l_, pl in zip(lo, plen)]
+            lo_a, hi_a = (ctypes.c_int64 * self.p)(*lo), (ctypes.c_int64 * self.p)(*hi)
+            self.raise_if_failed()
+            st = self._launch_stream()
+            check(self.lib.mp4x_ipc_fp8_allgather_check(dt, r, self.p, maxblk, soff, lo_a, hi_a, out),
+                  "mp4x_ipc_fp8_allgather")
+            self._fp8_stage(dt, out + lo[r] * es, plen[r], maxblk, soff, st)
+            edev = self._next_epoch(st)
+            check(self.lib.mp4x_ipc_fp8_allgather(dt, self._pp_data[0], self._pp_sig[0], r, self.p, maxblk, soff,
+                                                  lo_a, hi_a, out, self.epoch,
+                                                  self._blocks_for_waves(-(-maxblk // 4), view.dtype, "fp8ag"),
+                                                  edev, st), "mp4x_ipc_fp8_allgather")
+        return True
+
+    def _blocks_for_waves(self, waves: int, dtype, family: Optional[str] = None) -> int:
+        """Grid of the fused fp8 two-shot, or of ``family`` (8 waves per block).  On a GPU shared by
+        the ranks (rehearsals) the cap of this kernel's occupancy applies (:meth:`grid_cap`; its
+        40 KB LDS tile and register load fit fewer blocks per CU than the generic kernels)."""
         if not self.shared_gpu:
             return 0
-        return max(1, min(self.grid_cap("fp8n" if _FP8_NARROW else "fp8", dtype), -(-waves // 8)))
+        return max(1, min(self.grid_cap(family or ("fp8n" if _FP8_NARROW else "fp8"), dtype), -(-waves // 8)))
 
     def prepare_graph(self):
         """Move the epoch counter to device memory so hipGraph replays get fresh epochs.

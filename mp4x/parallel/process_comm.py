@@ -527,7 +527,9 @@ class ProcessCommSlave:
 
     # ================================================================ allgather
     def allgatherArray(self, arrData, operand: Operand, froms: Sequence[int], tos: Sequence[int]):
+        # (the memo key carries no codec: a call with the fp8 operand always takes the full path)
         if self._fast_ar and type(froms) is list and type(tos) is list and \
+                getattr(operand, "codec", None) != "fp8" and \
                 self._fast_plan_call("allgather", arrData, (tuple(froms), tuple(tos))):
             return arrData
         self._tick("allgatherArray")
@@ -537,7 +539,8 @@ class ProcessCommSlave:
             return arrData
         CommUtils.isfromsTosLegal(froms, tos)
         if _is_device_tensor(arrData):
-            return self.device.allgather(arrData, list(froms), list(tos), memo=self._fast_ar is not None)
+            return self.device.allgather(arrData, list(froms), list(tos), memo=self._fast_ar is not None,
+                                         operand=operand)
         buf = _host_view(arrData, operand)
         shm = self._shm_engine(buf, operand, None, tos[-1] - froms[0])
         if shm is not None and buf.flags.c_contiguous:
