@@ -84,6 +84,13 @@ int mp4x_keys_from16(const void* keys16, int64_t n, int64_t* keys, void* stream)
 // Block-scaled quantisation: scale[b] = amax(block b) / 448, q = fp8(x / scale).
 // block must be 256 (one wave, 4 elements per lane).  n must be a multiple of 4.
 int mp4x_quant_fp8(int dtype_in, const void* in, int64_t n, uint8_t* q, float* scales, void* stream);
+// The same quantiser with error feedback (k_quant_ef): per element x = (float)in + resid (one f32
+// add), (code, scale) = the quantisation of x exactly as above, resid = fma(-decode(code), scale, x),
+// stored as 0 where that is not finite (a NaN input resets its own element, a block with an
+// infinity the whole block).  resid: f32[n], read and written in place, 16-byte aligned, nothing at
+// or past n touched; in is not written; q / scales: whole blocks, as above.  MP4X_E_BADARG (nothing
+// launched) for n % 4 != 0, a NULL pointer, or in / resid off the 16-byte grid.
+int mp4x_quant_fp8_ef(int dtype_in, const void* in, int64_t n, float* resid, uint8_t* q, float* scales, void* stream);
 // out = dequant(q[0]) + ... + dequant(q[nin-1])  (f32 accumulate), optionally + out (accumulate=1).
 // If q_out != NULL the f32 result is also re-quantised into (q_out, s_out).
 int mp4x_dequant_reduce_fp8(int dtype_out, void* out, const uint8_t* const* qs, const float* const* scales,

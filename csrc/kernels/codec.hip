@@ -41,6 +41,78 @@ __global__ __launch_bounds__(kBlock) void k_quant(const void* __restrict__ in, i
   }
 }
 
+// K6 with error feedback: quantise x = in + resid and leave in resid what the codes dropped, so a
+// sequence of calls sends sum(in) to within one residual.  quant_block's arithmetic, statement for
+// statement (both are pinned bit for bit against tests/fp8_ref.py), with the code and the scale
+// kept in registers for the residual.  r = fma(-decode(code), scale, x) is an explicit FMA like
+// fp8_fma_acc; a residual that is not finite is stored as 0 (by comparison: NaN and +-inf both
+// fail it), so a NaN input resets its own element and an infinity, whose block has an infinite
+// scale, the whole block: one overflowed step does not poison the next.
+__device__ __forceinline__ void quant_block_ef(float (&x)[4], const float (&r)[4], uint32_t* q, float* scales,
+                                               int64_t blk, int lane) {
+  {
+#pragma clang fp contract(off)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) x[j] = x[j] + r[j];
+  }
+  float m = fmaxf(fmaxf(fabsf(x[0]), fabsf(x[1])), fmaxf(fabsf(x[2]), fabsf(x[3])));
+  m = wave_max(m);
+  const float scale = m > 0.0f ? m / kFp8Max : 1.0f;
+  const uint32_t w = pack_fp8(x, 1.0f / scale);
+  __builtin_nontemporal_store(w, q + blk * 64 + lane);
+  if (lane == 0) scales[blk] = scale;
+  const float d[4] = {__builtin_amdgcn_cvt_f32_fp8((int)w, 0), __builtin_amdgcn_cvt_f32_fp8((int)w, 1),
+                      __builtin_amdgcn_cvt_f32_fp8((int)w, 2), __builtin_amdgcn_cvt_f32_fp8((int)w, 3)};
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const float e = __builtin_fmaf(-d[j], scale, x[j]);
+    x[j] = fabsf(e) <= 3.402823466e+38f ? e : 0.0f;
+  }
+}
+
+// Same launch shape as k_quant; per block a lane also streams 16 bytes of residual in and out
+// (load4 / store4 <F32>: nontemporal, touched once), all 2 * QU loads issued before the first amax.
+template <int DT, int QU>
+__global__ __launch_bounds__(kBlock) void k_quant_ef(const void* __restrict__ in, int64_t n, float* __restrict__ resid,
+                                                     uint32_t* __restrict__ q, float* __restrict__ scales) {
+  const int lane = threadIdx.x & 63;
+  const int64_t nblk = (n + kQBlock - 1) / kQBlock;
+  const int64_t wave = wave_id();
+  const int64_t nwaves = ((int64_t)gridDim.x * kBlock) >> 6;
+  for (int64_t b0 = wave * QU; b0 < nblk; b0 += nwaves * QU) {
+    float x[QU][4], r[QU][4];
+    const int64_t e0 = b0 * kQBlock + lane * 4;
+    // QU whole blocks (wave-uniform): straight-line 16-byte loads.  With load4's tail branch
+    // between them the compiler waits for every earlier load before it issues the next one
+    // (the two sides of that branch share registers), so the tail form is kept for the last
+    // wave iteration alone.  A bound of e + 4 folds load4 / store4 to their vector side.
+    const bool whole = (b0 + QU) * kQBlock <= n;
+    if (whole) {
+#pragma unroll
+      for (int u = 0; u < QU; ++u) {
+        load4<DT>(in, e0 + u * kQBlock, e0 + u * kQBlock + 4, x[u]);
+        load4<MP4X_F32>(resid, e0 + u * kQBlock, e0 + u * kQBlock + 4, r[u]);
+      }
+    } else {
+#pragma unroll
+      for (int u = 0; u < QU; ++u)
+        if (b0 + u < nblk) {
+          load4<DT>(in, e0 + u * kQBlock, n, x[u]);
+          load4<MP4X_F32>(resid, e0 + u * kQBlock, n, r[u]);
+        }
+    }
+#pragma unroll
+    for (int u = 0; u < QU; ++u)
+      if (b0 + u < nblk) {
+        quant_block_ef(x[u], r[u], q, scales, b0 + u, lane);
+        if (whole)
+          store4<MP4X_F32>(resid, e0 + u * kQBlock, e0 + u * kQBlock + 4, x[u]);
+        else
+          store4<MP4X_F32>(resid, e0 + u * kQBlock, n, x[u]);   // nothing at or past n
+      }
+  }
+}
+
 template <int NIN> struct QIn { const uint32_t* q[NIN]; const float* s[NIN]; };
 
 // DU consecutive quant blocks per wave iteration: DU * NIN independent loads in flight.
@@ -97,6 +169,14 @@ static int launch_quant(const void* in, int64_t n, uint32_t* q, float* s, hipStr
   int64_t nblk = (n + kQBlock - 1) / kQBlock;
   const int g = codec_grid(nblk * 64, QU);        // a wave takes QU quant blocks per iteration
   hipLaunchKernelGGL((k_quant<DT, QU>), dim3(g), dim3(kBlock), 0, st, in, n, q, s);
+  return (int)hipGetLastError();
+}
+
+template <int DT>
+static int launch_quant_ef(const void* in, int64_t n, float* resid, uint32_t* q, float* s, hipStream_t st) {
+  int64_t nblk = (n + kQBlock - 1) / kQBlock;
+  const int g = codec_grid(nblk * 64, QU);
+  hipLaunchKernelGGL((k_quant_ef<DT, QU>), dim3(g), dim3(kBlock), 0, st, in, n, resid, q, s);
   return (int)hipGetLastError();
 }
 
@@ -616,6 +696,21 @@ extern "C" int mp4x_quant_fp8(int dtype_in, const void* in, int64_t n, uint8_t* 
     case MP4X_F32: return launch_quant<MP4X_F32>(in, n, qq, scales, st);
     case MP4X_BF16: return launch_quant<MP4X_BF16>(in, n, qq, scales, st);
     case MP4X_F16: return launch_quant<MP4X_F16>(in, n, qq, scales, st);
+    default: return MP4X_E_UNSUPPORTED;
+  }
+}
+
+extern "C" int mp4x_quant_fp8_ef(int dtype_in, const void* in, int64_t n, float* resid, uint8_t* q, float* scales,
+                                 void* stream) {
+  if (n <= 0) return 0;
+  if ((n & 3) || !in || !resid || !q || !scales) return MP4X_E_BADARG;
+  if (((uintptr_t)q & 3) || ((uintptr_t)in & 15) || ((uintptr_t)resid & 15)) return MP4X_E_BADARG;
+  hipStream_t st = (hipStream_t)stream;
+  uint32_t* qq = reinterpret_cast<uint32_t*>(q);
+  switch (dtype_in) {
+    case MP4X_F32: return launch_quant_ef<MP4X_F32>(in, n, resid, qq, scales, st);
+    case MP4X_BF16: return launch_quant_ef<MP4X_BF16>(in, n, resid, qq, scales, st);
+    case MP4X_F16: return launch_quant_ef<MP4X_F16>(in, n, resid, qq, scales, st);
     default: return MP4X_E_UNSUPPORTED;
   }
 }

@@ -81,6 +81,7 @@ class _Bucket:
             self.master = torch.nn.Parameter(mine.detach().to(master_dtype).clone())
         self.pending = len(params)
         self.launched = False
+        self.residual: Optional[torch.Tensor] = None      # error feedback of the fp8 gradient codec
 
 
 class ZeroOptimizer:
@@ -93,12 +94,21 @@ class ZeroOptimizer:
     quarter of the f32 bytes on every link, quantised ONCE — the compressed allreduce of
     ``models/ddp.py`` quantises twice); the parameter all-gather stays exact.  Strictly opt-in, for
     f32 / bf16 / f16 parameters (``ValueError`` for f64); where the compressed form does not
-    apply (no GPU mesh, ``MP4X_FP8_TRANSPORT=rccl``) the reduce-scatter is the exact one."""
+    apply (no GPU mesh, ``MP4X_FP8_TRANSPORT=rccl``) the reduce-scatter is the exact one.
+    ``error_feedback`` (with ``grad_codec="fp8"`` only, ``ValueError`` otherwise): every bucket keeps
+    an f32 residual of what its quantiser dropped and adds it to the next step's gradient before
+    quantising, so the sum of what was sent tracks the sum of the true gradients to within one
+    residual instead of drifting with the number of steps.  The residual is NOT sharded: every rank
+    quantises its whole local gradient, so it costs 4 bytes per gradient element on every rank.  It
+    moves only when a bucket's reduce-scatter is launched (``no_sync()`` passes leave it alone),
+    ``zero_grad()`` does not clear it, ``state_dict()`` carries it as ``"residuals"`` and ``close()``
+    drops it.  On the CPU or with one rank nothing is allocated and the option does nothing."""
 
     def __init__(self, comm, params: Iterable[torch.nn.Parameter], optimizer=torch.optim.AdamW,
                  average: bool = True, max_grad_norm: Optional[float] = None,
                  master_dtype: torch.dtype = torch.float32, bucket_mb: Optional[float] = None,
-                 overlap: Optional[bool] = None, grad_codec: Optional[str] = None, **optim_kwargs):
+                 overlap: Optional[bool] = None, grad_codec: Optional[str] = None, error_feedback: bool = False,
+                 **optim_kwargs):
         self.comm = comm
         self.p, self.r = comm.getSlaveNum(), comm.getRank()
         self.average = average
@@ -113,7 +123,10 @@ class ZeroOptimizer:
             raise ValueError(f"ZeroOptimizer: unknown grad_codec {grad_codec!r} (None or 'fp8')")
         if grad_codec and any(q.dtype == torch.float64 for q in params):
             raise ValueError("ZeroOptimizer: grad_codec needs f32 / bf16 / f16 parameters (got float64)")
+        if error_feedback and grad_codec != "fp8":
+            raise ValueError("ZeroOptimizer: error_feedback needs grad_codec='fp8'")
         self.grad_codec = grad_codec
+        self.error_feedback = bool(error_feedback)
         cap = int((bucket_mb or float(os.environ.get("MP4X_BUCKET_MB", 64))) * (1 << 20))
         runs: Dict[torch.dtype, List[List[torch.nn.Parameter]]] = {}
         for q in reversed(params):                       # backward order; identical on every rank
@@ -139,6 +152,9 @@ class ZeroOptimizer:
             for b in rs:
                 self.buckets.append(_Bucket(b, self.p, self.r, pa, ga, off, master_dtype, grad_codec))
                 off += self.buckets[-1].n
+        if self.error_feedback and self.cuda and self.p > 1:
+            for b in self.buckets:
+                b.residual = torch.zeros(b.n, dtype=torch.float32, device=b.grad.device)
         self._owner = {}
         self._hooks = []
         for b in self.buckets:
@@ -167,7 +183,13 @@ class ZeroOptimizer:
             ev.record()                                  # the bucket's gradients are complete here
             with torch.cuda.stream(self.stream):
                 self.stream.wait_event(ev)
-                self.comm.reduceScatterArray(b.grad, b.grad_operand, b.op, 0, [b.shard] * self.p)
+                self._rs(b)
+        else:
+            self._rs(b)
+
+    def _rs(self, b: _Bucket) -> None:
+        if b.residual is not None:
+            self.comm.reduceScatterArray(b.grad, b.grad_operand, b.op, 0, [b.shard] * self.p, residual=b.residual)
         else:
             self.comm.reduceScatterArray(b.grad, b.grad_operand, b.op, 0, [b.shard] * self.p)
 
@@ -247,17 +269,31 @@ class ZeroOptimizer:
     def state_dict(self) -> dict:
         """This rank's shard: the inner optimizer's state and the master slices (a sharded
         checkpoint — every rank saves its own; ``load_state_dict`` needs the same p and rank)."""
-        return {"p": self.p, "rank": self.r, "optim": self.optim.state_dict(),
-                "masters": [b.master.detach().cpu().clone() for b in self.buckets]}
+        sd = {"p": self.p, "rank": self.r, "optim": self.optim.state_dict(),
+              "masters": [b.master.detach().cpu().clone() for b in self.buckets]}
+        if self.error_feedback:
+            # the error-feedback residuals of this rank's WHOLE local gradient (not a shard); empty
+            # where none are kept (CPU, one rank)
+            if self.stream is not None:                   # a reduce-scatter still writing one
+                torch.cuda.current_stream().wait_stream(self.stream)
+            sd["residuals"] = [b.residual.detach().cpu().clone() for b in self.buckets if b.residual is not None]
+        return sd
 
     def load_state_dict(self, sd: dict) -> None:
         if sd["p"] != self.p or sd["rank"] != self.r:
             raise ValueError(f"shard checkpoint is for rank {sd['rank']}/{sd['p']}, this is {self.r}/{self.p}")
         if len(sd["masters"]) != len(self.buckets):
             raise ValueError("shard checkpoint has a different bucket layout")
+        kept = [b for b in self.buckets if b.residual is not None]
+        res = sd.get("residuals")
+        if kept and res is not None and (len(res) != len(kept) or
+                                         any(x.numel() != b.n for b, x in zip(kept, res))):
+            raise ValueError("shard checkpoint has a different residual layout")
         with torch.no_grad():
             for b, m in zip(self.buckets, sd["masters"]):
                 b.master.copy_(m)
+            for i, b in enumerate(kept):                  # a checkpoint without residuals: start from zeros
+                b.residual.copy_(res[i]) if res is not None else b.residual.zero_()
         self.optim.load_state_dict(sd["optim"])
         self._all_gather()                                # every rank's parameters from the restored slices
 
@@ -274,6 +310,7 @@ class ZeroOptimizer:
                 for q in b.params:
                     q.data = q.data.clone()
                     q.grad = None
+            b.residual = None
         self.buckets = []
         self._owner = {}
         if self._memalloc:
@@ -285,7 +322,7 @@ class ZeroOptimizer:
 def train_zero(comm, steps: int = 5, global_batch: int = 64, din: int = 64, hidden: int = 128, dout: int = 16,
                lr: float = 0.01, device="cpu", dtype=torch.float32, max_grad_norm=None,
                bucket_mb: Optional[float] = None, overlap: Optional[bool] = None, micro: int = 1,
-               grad_codec: Optional[str] = None) -> List[float]:
+               grad_codec: Optional[str] = None, error_feedback: bool = False) -> List[float]:
     """The MLP of :mod:`mp4x.models.mlp` trained data-parallel with AdamW under ZeroOptimizer
     (``micro`` gradient-accumulation micro-batches per step); returns the GLOBAL loss per step."""
     from .mlp import MLP, synthetic_batch
@@ -293,7 +330,8 @@ def train_zero(comm, steps: int = 5, global_batch: int = 64, din: int = 64, hidd
     torch.manual_seed(0)
     model = MLP(din, hidden, dout).to(device=device, dtype=dtype)
     opt = ZeroOptimizer(comm, model.parameters(), torch.optim.AdamW, lr=lr, weight_decay=0.01,
-                        max_grad_norm=max_grad_norm, bucket_mb=bucket_mb, overlap=overlap, grad_codec=grad_codec)
+                        max_grad_norm=max_grad_norm, bucket_mb=bucket_mb, overlap=overlap, grad_codec=grad_codec,
+                        error_feedback=error_feedback)
     losses = []
     shard = global_batch // p
     mb = shard // micro

@@ -151,6 +151,40 @@ def quant_fp8(x: torch.Tensor, q: Optional[torch.Tensor] = None, scales: Optiona
     return (q[:n] if own else q), scales
 
 
+def quant_fp8_ef(x: torch.Tensor, resid: torch.Tensor, q: Optional[torch.Tensor] = None,
+                 scales: Optional[torch.Tensor] = None, stream=None):
+    """:func:`quant_fp8` with error feedback: quantises ``x + resid`` (one f32 add) and leaves in
+    ``resid`` what the codes dropped, ``fma(-decode(code), scale, x + resid)``, for the next call.
+    ``resid`` is f32 with ``x.numel()`` elements, 16-byte aligned, updated in place; ``x`` is not
+    written.  Buffers and return value as :func:`quant_fp8`.
+
+    A non-finite residual element is stored as 0: a NaN input resets its own element, a block with
+    an infinity (its scale is infinite) resets the whole block.  With an all-``+0`` residual the
+    codes and scales are :func:`quant_fp8`'s, except that an input of ``-0.0`` encodes as ``+0.0``."""
+    _dev_check(x, resid, q, scales)
+    n = x.numel()
+    if n % 4:
+        raise ValueError("quant_fp8_ef: n must be a multiple of 4")
+    if resid.dtype != torch.float32 or resid.numel() != n:
+        raise ValueError(f"quant_fp8_ef: resid must be float32 with {n} elements "
+                         f"(got {resid.dtype}, {resid.numel()})")
+    if resid.data_ptr() % 16:
+        raise ValueError("quant_fp8_ef: resid must be 16-byte aligned")
+    nblk = (n + QBLOCK - 1) // QBLOCK
+    own = q is None
+    if own:
+        q = torch.empty(nblk * QBLOCK, dtype=torch.uint8, device=x.device)
+    if scales is None:
+        scales = torch.empty(nblk, dtype=torch.float32, device=x.device)
+    if q.dtype != torch.uint8 or scales.dtype != torch.float32:
+        raise ValueError("quant_fp8_ef: q must be uint8 and scales float32")
+    if q.numel() < nblk * QBLOCK or scales.numel() < nblk:
+        raise ValueError(f"quant_fp8_ef: q needs whole blocks ({nblk * QBLOCK} bytes for n = {n}) and scales {nblk}")
+    check(native.hip().mp4x_quant_fp8_ef(int(dtype_of_torch(x.dtype)), x.data_ptr(), n, resid.data_ptr(), q.data_ptr(),
+                                         scales.data_ptr(), stream_ptr(stream)), "mp4x_quant_fp8_ef")
+    return (q[:n] if own else q), scales
+
+
 def dequant_reduce_fp8(out: Optional[torch.Tensor], qs: Sequence[torch.Tensor], ss: Sequence[torch.Tensor], n: int,
                        accumulate: bool = False, q_out: Optional[torch.Tensor] = None,
                        s_out: Optional[torch.Tensor] = None, out_dtype=None, stream=None):

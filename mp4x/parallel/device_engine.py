@@ -1404,13 +1404,22 @@ class DeviceEngine(AutotuneMixin, ScheduleMixin, RootedMixin):
             torch.cuda.synchronize(self.device)
 
     # ================================================================== reduce-scatter
-    def reduce_scatter(self, arr: torch.Tensor, froms, tos, operator, operand=None, memo=None):
+    def reduce_scatter(self, arr: torch.Tensor, froms, tos, operator, operand=None, memo=None, residual=None):
         """``memo``: the public API's key tail for this call shape (``(frm, counts, operator,
-        codec, compress)``) — memoise the fused IPC reduce-scatter it runs for the API's fast path."""
+        codec, compress)``) — memoise the fused IPC reduce-scatter it runs for the API's fast path.
+
+        ``residual``: the error-feedback residual of the fp8 form (f32, one element per element of
+        the range, this rank's own; see ``IpcAllreduce.reduce_scatter_fp8``).  Only with the fp8
+        operand, SUM and a GPU tensor (``Mp4jException`` otherwise, on every rank alike); where the
+        fp8 form does not apply the call is the exact reduce-scatter and the residual keeps its
+        bits.  Such a call is never memoised."""
         flat = self._flat(arr)
         r = self.rank
         base = froms[0]
         whole = flat[base:tos[-1]]
+        if residual is not None:
+            memo = None
+            self._check_residual(residual, flat, whole.numel(), operator, operand)
         if whole.numel() == 0:
             return arr
         op = self._op(operator, whole)
@@ -1419,8 +1428,10 @@ class DeviceEngine(AutotuneMixin, ScheduleMixin, RootedMixin):
             memo = None     # the exact forms below must not be memoised under a key that carries the codec
             if not getattr(op, "is_custom", False) and op.code == OpCode.SUM:
                 inst = self._fp8_half_inst(flat, froms, tos)
-                if inst is not None and inst.reduce_scatter_fp8(flat, froms, tos):
+                if inst is not None and inst.reduce_scatter_fp8(flat, froms, tos, residual):
                     self._count("reduce_scatter.fp8.ipc")      # e4m3 on the links, quantised once
+                    if residual is not None:
+                        self._count("reduce_scatter.fp8.ef")   # ... with error feedback
                     return arr
         algo = self.select("reduce_scatter", whole.numel() * whole.element_size(), op, whole.dtype, operand)
         if algo in ("rccl", "a2a") and self._zc_ok(whole) and self._ipc_obj.reduce_scatter_registered(flat, froms,
@@ -1458,6 +1469,19 @@ class DeviceEngine(AutotuneMixin, ScheduleMixin, RootedMixin):
         else:
             self._reduce_scatter_a2a(flat, froms, tos, op)
         return arr
+
+    def _check_residual(self, residual, flat: torch.Tensor, n: int, operator, operand) -> None:
+        """The conditions of ``reduce_scatter(residual=...)``, all of them facts every rank shares."""
+        if getattr(operand, "codec", None) != "fp8":
+            raise Mp4jException("reduceScatterArray: residual= needs an operand with codec='fp8'")
+        if getattr(operator, "is_custom", False) or operator.code != OpCode.SUM:
+            raise Mp4jException("reduceScatterArray: residual= needs the SUM operator")
+        if not flat.is_cuda:
+            raise Mp4jException("reduceScatterArray: residual= needs a GPU tensor")
+        if not (torch.is_tensor(residual) and residual.is_cuda and residual.device == flat.device
+                and residual.dtype == torch.float32 and residual.is_contiguous() and residual.numel() == n):
+            raise Mp4jException(f"reduceScatterArray: the residual must be a contiguous float32 tensor of {n} "
+                                f"elements (counts' sum) on {flat.device}")
 
     # ================================================================== allgather
     def _fp8_half_inst(self, flat: torch.Tensor, froms, tos):

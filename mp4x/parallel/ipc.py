@@ -1325,27 +1325,49 @@ class IpcAllreduce(IpcForms):
             raise Mp4jException("IPC buffer too small for the fp8 reduce-scatter / all-gather")
         return int(b)
 
-    def _fp8_stage(self, dt: int, src: int, n: int, nblk: int, soff: int, st) -> None:
+    def _fp8_stage(self, dt: int, src: int, n: int, nblk: int, soff: int, st, resid: int = 0) -> None:
         """Quantise ``n`` elements at ``src`` into the own buffer on an ``nblk``-block layout (codes
-        at 0, scales at ``soff``); the blocks past the input are zeroed, as in the allreduce."""
+        at 0, scales at ``soff``); the blocks past the input are zeroed, as in the allreduce.
+        ``resid``: the address of these elements' f32 error-feedback residual (the quantiser adds
+        it to the input and leaves there what the codes dropped), 0 for none."""
         own = self._data.value
         used = -(-n // self.QBLOCK)
         if used < nblk:
             check(self.lib.mp4x_memset_async(own + used * self.QBLOCK, 0, (nblk - used) * self.QBLOCK, st), "fp8 q tail")
             check(self.lib.mp4x_memset_async(own + soff + used * 4, 0, (nblk - used) * 4, st), "fp8 scale tail")
-        if n:
+        if n and resid:
+            check(self.lib.mp4x_quant_fp8_ef(dt, src, n, resid, own, own + soff, st), "fp8 quant (error feedback)")
+        elif n:
             check(self.lib.mp4x_quant_fp8(dt, src, n, own, own + soff, st), "fp8 quant")
 
-    def reduce_scatter_fp8(self, view: torch.Tensor, froms, tos) -> bool:
+    def reduce_scatter_fp8(self, view: torch.Tensor, froms, tos, residual: Optional[torch.Tensor] = None) -> bool:
         """In place SUM reduce-scatter with the block-scaled e4m3 codec on the links:
         ``view[froms[r]:tos[r]]`` <- the f32 sum, in rank order, of every rank's quantised range,
         stored with one rounding; nothing else is written.  The range ``[froms[0], tos[-1])`` is
         quantised on ONE block grid counted from its start, and pieces (a range whose codes exceed
         the buffer) are cut on that grid, so the result does not depend on the buffer size.  Every
         rank runs the same pieces with the same grid, also where its own share is empty.  Returns
-        False (nothing done) when the call does not qualify (:meth:`fp8_range_ok`)."""
+        False (nothing done) when the call does not qualify (:meth:`fp8_range_ok`).
+
+        ``residual`` (error feedback): this rank's f32 residual of the range, ``tos[-1] - froms[0]``
+        elements indexed from the range start (the quantisation's grid).  The quantiser encodes
+        ``view + residual`` and leaves in ``residual`` what the codes dropped; nothing else of the
+        call changes.  A call that returns False leaves it untouched."""
+        if residual is not None:
+            n_res = tos[-1] - froms[0]
+            if not (torch.is_tensor(residual) and residual.is_cuda and residual.device == view.device
+                    and residual.dtype == torch.float32 and residual.is_contiguous() and residual.numel() == n_res):
+                raise Mp4jException(f"fp8 reduce-scatter: the residual must be a contiguous float32 tensor of "
+                                    f"{n_res} elements on {view.device}")
         if not self.fp8_range_ok(view, froms, tos):
             return False
+        if residual is not None and residual.data_ptr() % 16:
+            # an oddly offset residual on THIS rank: the same kernels on an aligned temporary
+            rtmp = torch.empty_like(residual)
+            rtmp.copy_(residual)
+            self.reduce_scatter_fp8(view, froms, tos, rtmp)
+            residual.copy_(rtmp)
+            return True
         flat = view.view(-1)
         base, end, r = froms[0], tos[-1], self.rank
         rng = flat[base:end]
@@ -1354,7 +1376,7 @@ class IpcAllreduce(IpcForms):
             tmp = torch.empty_like(rng)
             tmp.copy_(rng)
             rel_f, rel_t = [f - base for f in froms], [t - base for t in tos]
-            self.reduce_scatter_fp8(tmp, rel_f, rel_t)
+            self.reduce_scatter_fp8(tmp, rel_f, rel_t, residual)
             if rel_t[r] > rel_f[r]:
                 rng[rel_f[r]:rel_t[r]].copy_(tmp[rel_f[r]:rel_t[r]])
             return True
@@ -1364,6 +1386,7 @@ class IpcAllreduce(IpcForms):
         dt = int(dtype_of_torch(view.dtype))
         cap = self._fp8_half_blocks()
         nblk_all = -(-n // Q)
+        resid = residual.data_ptr() if residual is not None else 0
         for b0 in range(0, nblk_all, cap):
             nblk = min(cap, nblk_all - b0)
             e0 = b0 * Q                                   # the piece's first element, from the range start
@@ -1379,7 +1402,7 @@ class IpcAllreduce(IpcForms):
             # every refusal BEFORE the epoch moves: a refused piece leaves this rank's epoch in step
             check(self.lib.mp4x_ipc_fp8_reduce_scatter_check(dt, r, self.p, nblk, soff, lo_a, hi_a, src),
                   "mp4x_ipc_fp8_reduce_scatter")
-            self._fp8_stage(dt, src, m, nblk, soff, st)
+            self._fp8_stage(dt, src, m, nblk, soff, st, resid + e0 * 4 if resid else 0)
             edev = self._next_epoch(st)
             check(self.lib.mp4x_ipc_fp8_reduce_scatter(dt, self._pp_data[0], self._pp_sig[0], r, self.p, nblk, soff,
                                                        lo_a, hi_a, src, self.epoch,

@@ -656,7 +656,18 @@ class ProcessCommSlave:
         return self.engine.tree_scatter_maps(blocks, operand, rootRank)
 
     # ================================================================ reduce-scatter
-    def reduceScatterArray(self, arrData, operand: Operand, operator, frm: int, counts: Sequence[int]):
+    def reduceScatterArray(self, arrData, operand: Operand, operator, frm: int, counts: Sequence[int],
+                           residual=None):
+        """``residual`` (extension, error feedback for the fp8 wire codec): this rank's f32 GPU
+        tensor of ``sum(counts)`` elements.  The fp8 form quantises ``arrData + residual`` and
+        leaves in ``residual`` what the codes dropped, so that over a sequence of calls the sum of
+        what was sent tracks the sum of the inputs to within one residual.  Valid only with an
+        operand whose ``codec == "fp8"``, the SUM operator and a GPU tensor (``Mp4jException``
+        otherwise, on every rank); where the fp8 form does not apply (no mesh,
+        ``MP4X_FP8_TRANSPORT=rccl``, offsets off the 16-byte grid) the call is the exact
+        reduce-scatter and the residual is left untouched."""
+        if residual is not None:
+            return self._reduce_scatter_ef(arrData, operand, operator, frm, counts, residual)
         fast = self._fast_ar
         tail = None
         if fast is not None and type(counts) is list:
@@ -688,6 +699,25 @@ class ProcessCommSlave:
             return arrData
         self.engine.ring_reduce_scatter(buf, froms, tos, operand, operator)
         return arrData
+
+    def _reduce_scatter_ef(self, arrData, operand: Operand, operator, frm: int, counts, residual):
+        """``reduceScatterArray(residual=...)``: always the full path (never the memoised native
+        launch, whose key carries no residual), refused before any collective work."""
+        from ..operators import OpCode
+        if getattr(operand, "codec", None) != "fp8":
+            raise Mp4jException("reduceScatterArray: residual= needs an operand with codec='fp8'")
+        if getattr(operator, "is_custom", False) or operator.code != OpCode.SUM:
+            raise Mp4jException("reduceScatterArray: residual= needs the SUM operator")
+        if not _is_device_tensor(arrData):
+            raise Mp4jException("reduceScatterArray: residual= needs a GPU tensor")
+        self._tick("reduceScatterArray")
+        self._check_len(counts, "counts")
+        CommUtils.isFromCountsLegal(frm, counts)
+        froms = CommUtils.getFromsFromCount(frm, counts, self.slaveNum)
+        tos = CommUtils.getTosFromCount(frm, counts, self.slaveNum)
+        if self.slaveNum == 1:
+            return arrData
+        return self.device.reduce_scatter(arrData, froms, tos, operator, operand, memo=None, residual=residual)
 
     def reduceScatterMap(self, mapDataList: List[Dict], operand: Operand, operator) -> Dict:
         self._tick("reduceScatterMap")
