@@ -122,6 +122,21 @@ int mp4x_ipc_fp8_allgather(int dtype, void* const* data_ptrs, void* const* signa
                            uint32_t epoch, int blocks, const uint32_t* epoch_dev, void* stream);
 int mp4x_ipc_fp8_allgather_check(int dtype, int rank, int p, int64_t maxblk, int64_t soff, const int64_t* seg_lo,
                                  const int64_t* seg_hi, const void* out);
+// Ragged all-to-all with the fp8 codec on the links (dtype = f32 / bf16 / f16): every rank
+// quantised its WHOLE send buffer, flattened, on one block grid counted from its first element
+// (q bytes at 0, f32 scales at `soff` in EVERY rank's buffer; nblk_peer[k] = the quant blocks of
+// rank k's send, which bound the reads).  This rank receives, from every peer k, the elements
+// [elo[k], ehi[k]) of k's buffer at out[dst[k] ...] (elements, multiples of 4; the dst ranges in
+// rank order without overlap; `out` 16-B aligned), dequantised with one rounding; nothing else is
+// written.  `blocks` >= 1 and the same on every rank: the caller sizes it from the largest
+// (sender, receiver) segment of the whole count matrix, which one rank's arguments do not show.
+// _check: every refusal of the call without launching; the launcher runs it first.
+int mp4x_ipc_fp8_alltoall(int dtype, void* const* data_ptrs, void* const* signal_ptrs, int rank, int p,
+                          int64_t soff, const int64_t* elo, const int64_t* ehi, const int64_t* dst,
+                          const int64_t* nblk_peer, void* out, uint32_t epoch, int blocks,
+                          const uint32_t* epoch_dev, void* stream);
+int mp4x_ipc_fp8_alltoall_check(int dtype, int rank, int p, int64_t soff, const int64_t* elo, const int64_t* ehi,
+                                const int64_t* dst, const int64_t* nblk_peer, const void* out);
 // Does the IPC allreduce have a kernel for (dtype, op)?  1 / 0.
 int mp4x_ipc_op_supported(int dtype, int op);
 
@@ -163,7 +178,7 @@ int mp4x_ipc_copy_plan_check(int rank, int p, const int64_t* stage, int nstage, 
 // Blocks per CU the occupancy API admits for the kernel such a call launches: the shared-GPU
 // co-residency budget (mp4x/parallel/occupancy.py).  _misc families: 0 = the ragged all-gather,
 // 1 = the copy plan, 2 / 3 = the fused fp8 two-shot, wide / narrow (dtype = the output dtype),
-// 4 / 5 = the fp8 reduce-scatter / all-gather halves.
+// 4 / 5 = the fp8 reduce-scatter / all-gather halves, 6 = the fp8 ragged all-to-all.
 int mp4x_ipc_occupancy_ar(int algo, int dtype, int op, int p, int* blocks_per_cu);
 int mp4x_ipc_occupancy_push(int dtype, int op, int p, int* blocks_per_cu);
 int mp4x_ipc_occupancy_rs(int dtype, int op, int p, int* blocks_per_cu);

@@ -370,6 +370,77 @@ __global__ __launch_bounds__(kIpcThreads) void k_ipc_fp8_ag(IpcPtrs P, Signal* s
   block_barrier(P, 2, rank, p, epoch, self);
 }
 
+// Ragged all-to-all: rank k quantised its WHOLE send buffer (rows grouped by destination,
+// flattened) on ONE block grid counted from the buffer's first element (q bytes at 0, scales at
+// `soff`, which comes from the largest send of any rank).  This rank pulls from every peer k the
+// quant blocks that touch k's segment for it, [S.elo[k], S.ehi[k]) of k's buffer, and dequantises
+// them to out[S.dst[k] ...] with one rounding; a block that straddles two destinations is decoded
+// by both receivers and stored by each inside its own segment only (the reduce-scatter's LO
+// store at the front, the element bound at the back).  Every rank launches the same grid (sized
+// by the caller from the largest segment anywhere in the count matrix), also when it receives
+// nothing; the wave steps are this rank's own, the barriers are per block.
+template <int DT, int NR>
+__global__ __launch_bounds__(kIpcThreads) void k_ipc_fp8_a2a(IpcPtrs P, Signal* self, int rank, A2aSegs S,
+                                                              int64_t soff, void* __restrict__ out,
+                                                              uint32_t epoch, const uint32_t* epoch_dev) {
+  constexpr int p = NR;
+  using ST = typename Elem<DT>::S;
+  MP4X_DASSERT(rank >= 0 && rank < NR && blockIdx.x < kIpcMaxBlocks);
+  MP4X_DASSERT(soff >= 0 && (soff & 15) == 0);
+  __shared__ __attribute__((aligned(16))) float s_tile[kIpcThreads * kFp8LdsPitch];
+  epoch = resolve_epoch(epoch, epoch_dev);
+  if (!block_barrier(P, 0, rank, p, epoch, self)) return;
+  const int lane = threadIdx.x & 63;
+  const int g = lane >> 4;
+  const int sub = lane & 15;
+  constexpr int kWaves = kIpcThreads / 64;
+  float* tile = s_tile + (threadIdx.x >> 6) * 64 * kFp8LdsPitch;
+  const int64_t w0 = (int64_t)blockIdx.x * kWaves + (threadIdx.x >> 6);
+  const int64_t nw = (int64_t)gridDim.x * kWaves;
+  int64_t cb0[NR], cbe[NR];                              // quant blocks of peer k's grid that touch its segment
+  int64_t nquad = 0;                                     // wave steps over the largest of them
+#pragma unroll
+  for (int k = 0; k < NR; ++k) {
+    MP4X_DASSERT(S.elo[k] >= 0 && S.elo[k] <= S.ehi[k] && S.dst[k] >= 0);
+    MP4X_DASSERT(((S.elo[k] | S.ehi[k] | S.dst[k]) & 3) == 0);
+    cb0[k] = S.elo[k] / kQBlock;
+    cbe[k] = S.ehi[k] > S.elo[k] ? (S.ehi[k] + kQBlock - 1) / kQBlock : cb0[k];
+    MP4X_DASSERT(soff >= cbe[k] * kQBlock);
+    const int64_t q4 = (cbe[k] - cb0[k] + 3) / 4;
+    nquad = q4 > nquad ? q4 : nquad;
+  }
+  for (int64_t t = w0; t < nquad; t += nw) {
+    u32x4 w[NR];
+    float sc[NR];
+#pragma unroll
+    for (int k = 0; k < NR; ++k) {                        // every peer's 16 bytes in flight at once
+      const u32x4* q = reinterpret_cast<const u32x4*>(P.data[k]);
+      const int64_t j = cb0[k] + t * 4 + g;               // quant block on peer k's grid
+      const bool live = j < cbe[k];
+      const int64_t b = live ? j : cb0[k];
+      MP4X_DASSERT(b >= 0 && (!live || (b + 1) * kQBlock <= soff));
+      w[k] = live ? q[b * 16 + sub] : u32x4{0u, 0u, 0u, 0u};
+      sc[k] = live ? reinterpret_cast<const float*>(reinterpret_cast<const char*>(q) + soff)[b] : 0.0f;
+    }
+#pragma unroll
+    for (int k = 0; k < NR; ++k) {
+      if (cb0[k] + t * 4 >= cbe[k]) continue;             // wave-uniform: segment k ends before this step
+      float y[16];
+#pragma unroll
+      for (int d = 0; d < 4; ++d) {
+        // the codec's one-input dequant-reduce, fma(code, scale, +0), as in the all-gather
+        float yy[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+        fp8_fma_acc(w[k][d], sc[k], yy);
+        y[4 * d] = yy[0]; y[4 * d + 1] = yy[1]; y[4 * d + 2] = yy[2]; y[4 * d + 3] = yy[3];
+      }
+      // element e of peer k's buffer lands at out[dst[k] + e - elo[k]]
+      fp8_wave_store<DT, true>(tile, y, lane, reinterpret_cast<ST*>(out) + (S.dst[k] - S.elo[k]), cb0[k] + t * 4,
+                               cbe[k], S.ehi[k], S.elo[k]);
+    }
+  }
+  block_barrier(P, 2, rank, p, epoch, self);
+}
+
 // The r1 form (4 bytes per lane per peer, one wave per quant block), kept for A/B measurement
 // (MP4X_FP8_NARROW=1); bit-identical results.
 template <int DT, int NR>
@@ -728,6 +799,64 @@ extern "C" int mp4x_ipc_fp8_allgather(int dtype, void* const* data_ptrs, void* c
   });
 }
 
+extern "C" int mp4x_ipc_fp8_alltoall_check(int dtype, int rank, int p, int64_t soff, const int64_t* elo,
+                                           const int64_t* ehi, const int64_t* dst, const int64_t* nblk_peer,
+                                           const void* out) {
+  if (dtype != MP4X_F32 && dtype != MP4X_BF16 && dtype != MP4X_F16) return MP4X_E_UNSUPPORTED;
+  if (p < 2 || p > kIpcMaxRanks || rank < 0 || rank >= p) return MP4X_E_BADARG;
+  if (!elo || !ehi || !dst || !nblk_peer || ((uintptr_t)out & 15)) return MP4X_E_BADARG;
+  int64_t maxblk = 0, end = 0;
+  for (int k = 0; k < p; ++k) {
+    if (nblk_peer[k] < 0) return MP4X_E_BADARG;
+    if (nblk_peer[k] > maxblk) maxblk = nblk_peer[k];
+  }
+  if (soff < 0 || (soff & 15) || soff < maxblk * kQBlock) return MP4X_E_BADARG;    // scales after the q bytes
+  for (int k = 0; k < p; ++k) {
+    // not descending, inside peer k's quantised blocks, whole 4-element groups on both sides
+    if (elo[k] < 0 || ehi[k] < elo[k] || ehi[k] > nblk_peer[k] * kQBlock) return MP4X_E_BADARG;
+    if ((elo[k] | ehi[k] | dst[k]) & 3) return MP4X_E_BADARG;
+    if ((dst[k] - elo[k]) & 3) return MP4X_E_BADARG;     // store4's vector path stays aligned
+    if (dst[k] < end) return MP4X_E_BADARG;              // source-rank order, no overlap in `out`
+    end = dst[k] + (ehi[k] - elo[k]);
+    if (ehi[k] > elo[k] && !out) return MP4X_E_BADARG;
+  }
+  return 0;
+}
+
+extern "C" int mp4x_ipc_fp8_alltoall(int dtype, void* const* data_ptrs, void* const* signal_ptrs, int rank, int p,
+                                     int64_t soff, const int64_t* elo, const int64_t* ehi, const int64_t* dst,
+                                     const int64_t* nblk_peer, void* out, uint32_t epoch, int blocks,
+                                     const uint32_t* epoch_dev, void* stream) {
+  if (int e = mp4x_ipc_fp8_alltoall_check(dtype, rank, p, soff, elo, ehi, dst, nblk_peer, out)) return e;
+  // this rank sees its own column of the count matrix only: the grid, which must be the same on
+  // every rank (per-block barriers), is the caller's
+  if (blocks < 1) return MP4X_E_BADARG;
+  if (blocks > kIpcMaxBlocks) blocks = kIpcMaxBlocks;
+  IpcPtrs P;
+  if (int e = ipc_prepare(data_ptrs, signal_ptrs, rank, p, &P)) return e;
+  A2aSegs S;
+  for (int k = 0; k < kIpcMaxRanks; ++k) {
+    S.elo[k] = k < p ? elo[k] : 0;
+    S.ehi[k] = k < p ? ehi[k] : 0;
+    S.dst[k] = k < p ? dst[k] : 0;
+  }
+  Signal* self = (Signal*)signal_ptrs[rank];
+  hipStream_t st = (hipStream_t)stream;
+  return with_nr(p, [&](auto nrc) {
+    constexpr int NR = decltype(nrc)::value;
+#define MP4X_FP8A2A_CASE(DT)                                                                                   \
+  case DT:                                                                                                     \
+    hipLaunchKernelGGL((k_ipc_fp8_a2a<DT, NR>), dim3(blocks), dim3(kIpcThreads), 0, st, P, self, rank, S, soff, \
+                       out, epoch, epoch_dev);                                                                 \
+    return (int)hipGetLastError();
+    switch (dtype) {
+      MP4X_FP8A2A_CASE(MP4X_F32) MP4X_FP8A2A_CASE(MP4X_BF16) MP4X_FP8A2A_CASE(MP4X_F16)
+      default: return (int)MP4X_E_UNSUPPORTED;
+    }
+#undef MP4X_FP8A2A_CASE
+  });
+}
+
 extern "C" int mp4x_memset_async(void* dst, int value, size_t bytes, void* stream) {
   return (int)hipMemsetAsync(dst, value, bytes, (hipStream_t)stream);
 }
@@ -795,6 +924,14 @@ extern "C" int mp4x_ipc_occupancy_misc(int family, int dtype, int p, int* blocks
                                       : occ_min(k_ipc_fp8_ag<MP4X_BF16, NR>, &m); return 0;
           case MP4X_F16: family == 4 ? occ_min(k_ipc_fp8_rs<MP4X_F16, NR>, &m)
                                      : occ_min(k_ipc_fp8_ag<MP4X_F16, NR>, &m); return 0;
+          default: return (int)MP4X_E_UNSUPPORTED;
+        }
+      }
+      if (family == 6) {                                 // the fp8 ragged all-to-all
+        switch (dtype) {
+          case MP4X_F32: occ_min(k_ipc_fp8_a2a<MP4X_F32, NR>, &m); return 0;
+          case MP4X_BF16: occ_min(k_ipc_fp8_a2a<MP4X_BF16, NR>, &m); return 0;
+          case MP4X_F16: occ_min(k_ipc_fp8_a2a<MP4X_F16, NR>, &m); return 0;
           default: return (int)MP4X_E_UNSUPPORTED;
         }
       }

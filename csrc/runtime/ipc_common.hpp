@@ -155,6 +155,15 @@ struct Segs {
   int64_t hi[kIpcMaxRanks];
 };
 
+// The fp8 ragged all-to-all, as one receiver sees it: from peer k's quantised send buffer the
+// elements [elo[k], ehi[k]) (counted from the buffer's first element, multiples of 4) land at
+// element dst[k] of the receive tensor.
+struct A2aSegs {
+  int64_t elo[kIpcMaxRanks];
+  int64_t ehi[kIpcMaxRanks];
+  int64_t dst[kIpcMaxRanks];
+};
+
 // Lane t's peer Signal block: a select chain over the kernel argument's pointers (held in SGPRs)
 // instead of P.sig[t], whose per-lane index made every barrier a vector load from the kernarg
 // segment before the flag store.

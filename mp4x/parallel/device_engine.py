@@ -1572,12 +1572,20 @@ class DeviceEngine(AutotuneMixin, ScheduleMixin, RootedMixin):
         self._count("allreduce_map")
         return allreduce_map_device(self, mapData, operator)
 
-    def all_to_all_v(self, send: torch.Tensor, send_counts: List[int], recv: Optional[torch.Tensor] = None):
-        """Ragged all-to-all over rows of ``send`` (rows grouped by destination)."""
+    def all_to_all_v(self, send: torch.Tensor, send_counts: List[int], recv: Optional[torch.Tensor] = None,
+                     operand=None):
+        """Ragged all-to-all over rows of ``send`` (rows grouped by destination).  An ``operand``
+        with ``codec="fp8"`` asks for e4m3 on the links (:meth:`_all_to_all_v_fp8`); where that
+        form does not apply, and without it, the call is the exact one."""
         self._count("all_to_all_v")
         if sum(send_counts) != send.shape[0]:
             raise Mp4jException(f"sendCounts sum {sum(send_counts)} != rows {send.shape[0]}")
-        got = self._all_to_all_v_ipc(send, send_counts, recv)
+        mat = None
+        if getattr(operand, "codec", None) == "fp8":
+            got, mat = self._all_to_all_v_fp8(send, send_counts, recv)
+            if got is not None:
+                return got
+        got = self._all_to_all_v_ipc(send, send_counts, recv, mat)
         if got is not None:
             return got
         sc = torch.tensor(send_counts, dtype=torch.int64, device=self.device if self.backend == "nccl" else "cpu")
@@ -1592,21 +1600,64 @@ class DeviceEngine(AutotuneMixin, ScheduleMixin, RootedMixin):
         self.coll.all_to_all_single(recv, send.contiguous(), recv_counts, list(send_counts))
         return recv, recv_counts
 
-    def _all_to_all_v_ipc(self, send: torch.Tensor, send_counts: List[int], recv: Optional[torch.Tensor]):
-        """The all-to-all-v as one IPC copy-plan kernel (sparse._ipc_rows_alltoallv) when the rows
-        are whole 16-byte vectors and the largest rank's payload fits a staging buffer; the count
-        matrix comes from one small all-gather.  Every condition is rank-independent (shape,
-        dtype, environment, the gathered counts), so every rank takes the same path; None when
-        the call does not qualify."""
-        from . import sparse
+    @staticmethod
+    def _row_width(send: torch.Tensor) -> int:
         width = 1
         for d in send.shape[1:]:
             width *= int(d)
+        return width
+
+    def _all_to_all_v_fp8(self, send: torch.Tensor, send_counts: List[int], recv: Optional[torch.Tensor]):
+        """The all-to-all-v with the block-scaled e4m3 codec on the links
+        (``IpcAllreduce.alltoall_fp8``): a GPU tensor of f32 / bf16 / f16 (the tensor's dtype
+        decides, not the operand's) whose rows are a multiple of 4 elements, the IPC mesh of the
+        exact form (:meth:`_all_to_all_v_ipc`), ``MP4X_FP8_TRANSPORT`` not ``rccl``, and the
+        largest send of any rank, quantised, inside one staging buffer.  Every condition is
+        rank-independent.  Returns ``(result or None, count matrix or None)``: a declined call
+        hands the matrix it gathered to the exact form, which then does not gather it again."""
+        from . import sparse
+        from .ipc import IpcAllreduce
+        width = self._row_width(send)
+        if self.p < 2 or not send.is_cuda or send.dtype not in IpcAllreduce.FP8_DTYPES or width == 0 or width % 4 \
+                or self.algo not in ("", "auto", "ipc") \
+                or os.environ.get("MP4X_FP8_TRANSPORT", "auto").lower() == "rccl" \
+                or not sparse._sparse_ipc_ok(self, send):
+            return None, None
+        mat = sparse._count_matrix(self, torch.tensor(list(send_counts), dtype=torch.int64, device=send.device))
+        recv_counts = [mat[j][self.rank] for j in range(self.p)]
+        shape = (sum(recv_counts),) + tuple(send.shape[1:])
+        if recv is not None and tuple(recv.shape) != shape:
+            raise Mp4jException(f"recvData shape {tuple(recv.shape)} != {shape}")
+        maxblk = -(-max(sum(row) for row in mat) * width // IpcAllreduce.QBLOCK)
+        inst = sparse._ipc_inst(self, maxblk * (IpcAllreduce.QBLOCK + 4) + 16)     # codes + scales + the pad
+        if inst is None:
+            return None, mat
+        # a receive tensor of THIS rank that the kernel cannot write directly (another dtype, not
+        # contiguous, another device) must not change the path: the same kernels, then a copy
+        direct = recv is not None and recv.dtype == send.dtype and recv.is_contiguous() and recv.device == send.device
+        out = recv if direct else torch.empty(shape, dtype=send.dtype, device=send.device)
+        if not inst.alltoall_fp8(send.reshape(send.shape[0], width), mat, out.view(shape[0], width)):
+            return None, mat
+        if recv is not None and not direct:
+            recv.copy_(out)
+        self._count("all_to_all_v.fp8.ipc")            # e4m3 on the links
+        return (recv if recv is not None else out, recv_counts), mat
+
+    def _all_to_all_v_ipc(self, send: torch.Tensor, send_counts: List[int], recv: Optional[torch.Tensor],
+                          mat=None):
+        """The all-to-all-v as one IPC copy-plan kernel (sparse._ipc_rows_alltoallv) when the rows
+        are whole 16-byte vectors and the largest rank's payload fits a staging buffer; the count
+        matrix comes from one small all-gather (``mat``: already gathered by the fp8 form, which
+        declined).  Every condition is rank-independent (shape, dtype, environment, the gathered
+        counts), so every rank takes the same path; None when the call does not qualify."""
+        from . import sparse
+        width = self._row_width(send)
         rb = width * send.element_size()          # bytes per row
         if rb == 0 or rb % 16 or self.algo not in ("", "auto", "ipc") or not send.is_cuda or \
                 not sparse._sparse_ipc_ok(self, send):
             return None
-        mat = sparse._count_matrix(self, torch.tensor(list(send_counts), dtype=torch.int64, device=send.device))
+        if mat is None:
+            mat = sparse._count_matrix(self, torch.tensor(list(send_counts), dtype=torch.int64, device=send.device))
         recv_counts = [mat[j][self.rank] for j in range(self.p)]
         shape = (sum(recv_counts),) + tuple(send.shape[1:])
         if recv is not None and tuple(recv.shape) != shape:

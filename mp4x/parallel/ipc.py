@@ -17,7 +17,7 @@ import contextlib
 import ctypes
 import logging
 import os
-from typing import List, Optional
+from typing import List, NamedTuple, Optional
 
 import torch
 
@@ -192,6 +192,16 @@ class FastAr(ctypes.Structure):
                 ("signal_ptrs", c_void_p), ("rank", ctypes.c_int32), ("p", ctypes.c_int32),
                 ("slot_base", ctypes.c_int64), ("slot_vecs", ctypes.c_int64), ("order", c_void_p),
                 ("own_err", c_void_p)]
+
+
+class Fp8A2aPlan(NamedTuple):
+    """One rank's geometry of the fp8 ragged all-to-all (:meth:`IpcAllreduce.fp8_a2a_plan`)."""
+    elo: List[int]
+    ehi: List[int]
+    dst: List[int]
+    nblk_peer: List[int]
+    soff: int
+    steps: int
 
 
 class _Reg:
@@ -487,7 +497,7 @@ class IpcAllreduce(IpcForms):
             self.set_spin(old)
 
     # ---------------------------------------------------------------- co-residency grid caps
-    _OCC_FAMILY = {"gather": 0, "plan": 1, "fp8": 2, "fp8n": 3, "fp8rs": 4, "fp8ag": 5}
+    _OCC_FAMILY = {"gather": 0, "plan": 1, "fp8": 2, "fp8n": 3, "fp8rs": 4, "fp8ag": 5, "fp8a2a": 6}
 
     def grid_cap(self, family: str, dtype=None, op=None) -> int:
         """Largest grid a launch of ``family`` ((dtype, op) kernel; see parallel/occupancy.py)
@@ -1449,6 +1459,97 @@ class IpcAllreduce(IpcForms):
                                                   lo_a, hi_a, out, self.epoch,
                                                   self._blocks_for_waves(-(-maxblk // 4), view.dtype, "fp8ag"),
                                                   edev, st), "mp4x_ipc_fp8_allgather")
+        return True
+
+    # ---------------------------------------------------------------- the fp8 ragged all-to-all
+    # alltoallArray with the fp8 operand (csrc/runtime/ipc.hip k_ipc_fp8_a2a): quantise the whole
+    # send buffer into the own buffer (K6, one launch), then ONE kernel with a start and an end
+    # barrier in which every rank pulls and dequantises its block range of every peer.
+    @classmethod
+    def fp8_a2a_plan(cls, mat, width: int, rank: int, cap_blocks: int) -> Optional[Fp8A2aPlan]:
+        """The geometry of one fp8 all-to-all on ``rank`` — pure, no device work.  ``mat[k][j]`` =
+        rows of ``width`` elements (a multiple of 4) rank k sends to rank j; rank k's send buffer,
+        flattened, is quantised on one 256-element block grid counted from its first element.
+        From peer k this rank takes the elements ``[elo[k], ehi[k])`` of that grid to element
+        ``dst[k]`` of its receive tensor (source-rank order); ``nblk_peer[k]`` = the quant blocks of
+        k's whole send; ``soff`` (scales' byte offset, from the largest send) and ``steps`` (wave
+        steps of four quant blocks over the largest (sender, receiver) segment of the matrix, which
+        sizes the grid) are the same on every rank.  None when the largest send exceeds
+        ``cap_blocks`` quant blocks (rank-independent)."""
+        Q = cls.QBLOCK
+        p = len(mat)
+        if width <= 0 or width % 4:
+            raise Mp4jException("fp8 all-to-all: the row width must be a positive multiple of 4 elements")
+        nblk_peer = [-(-(sum(row) * width) // Q) for row in mat]
+        maxblk = max(nblk_peer)
+        if maxblk > cap_blocks:
+            return None
+        elo, ehi, dst, o, seg = [], [], [], 0, 0
+        for k in range(p):
+            lo = 0
+            for j in range(p):
+                hi = lo + mat[k][j] * width
+                if hi > lo:
+                    seg = max(seg, -(-hi // Q) - lo // Q)      # the blocks that touch k's segment for j
+                if j == rank:
+                    elo.append(lo)
+                    ehi.append(hi)
+                    dst.append(o)
+                    o += hi - lo
+                lo = hi
+        return Fp8A2aPlan(elo, ehi, dst, nblk_peer, (maxblk * Q + 15) // 16 * 16, -(-seg // 4))
+
+    def alltoall_fp8(self, send2d: torch.Tensor, mat, out: torch.Tensor) -> bool:
+        """Ragged all-to-all with the block-scaled e4m3 codec on the links.  ``send2d`` = this
+        rank's rows ``[sum(mat[rank]), w]`` grouped by destination, ``out`` = ``[sum of column
+        rank, w]``: the rows of every peer for this rank, in source-rank order, dequantised with
+        ONE rounding to the tensor's dtype.  The whole send buffer is quantised once, flattened, on
+        ONE block grid counted from its first element, so a quant block may straddle rows (unless w
+        is a multiple of 256) and destinations: a row's decoded values depend on its neighbours in
+        the block, as in the reduce-scatter; both receivers of a shared block decode it and each
+        stores its own part.  Nothing outside ``out`` is written and ``send2d`` keeps its bits.
+        Every rank launches the same grid, also when it receives nothing.  Returns False (nothing
+        done, the epoch unmoved) when the call does not qualify — f32 / bf16 / f16, w % 4 == 0, the
+        largest send of any rank fits the buffer in one piece — all of it rank-independent; a
+        tensor off the 16-byte grid on this rank runs the same kernels on an aligned temporary."""
+        w = int(send2d.shape[1]) if send2d.dim() == 2 else 0
+        if send2d.dtype not in self.FP8_DTYPES or out.dtype != send2d.dtype or not send2d.is_cuda \
+                or w == 0 or w % 4 or len(mat) != self.p:
+            return False
+        plan = self.fp8_a2a_plan(mat, w, self.rank, self._fp8_half_blocks())
+        if plan is None:
+            return False
+        r = self.rank
+        n_send, n_recv = sum(mat[r]) * w, plan.dst[-1] + plan.ehi[-1] - plan.elo[-1]
+        if send2d.numel() != n_send or out.numel() != n_recv:
+            raise Mp4jException(f"fp8 all-to-all: {send2d.numel()} send / {out.numel()} receive elements, the "
+                                f"count matrix says {n_send} / {n_recv}")
+        if max(plan.nblk_peer) == 0:
+            return True                                   # nobody sends anything (every rank sees that)
+        if not send2d.is_contiguous() or send2d.data_ptr() % 16:
+            # an oddly offset send tensor on THIS rank: the same kernels on an aligned copy
+            send2d = send2d.clone(memory_format=torch.contiguous_format)
+        if not out.is_contiguous() or out.data_ptr() % 16:
+            tmp = torch.empty(out.shape, dtype=out.dtype, device=out.device)
+            self.alltoall_fp8(send2d, mat, tmp)
+            out.copy_(tmp)
+            return True
+        I64 = ctypes.c_int64 * self.p
+        elo, ehi, dst, nbp = I64(*plan.elo), I64(*plan.ehi), I64(*plan.dst), I64(*plan.nblk_peer)
+        dt = int(dtype_of_torch(send2d.dtype))
+        self.raise_if_failed()
+        st = self._launch_stream()
+        # every refusal BEFORE the epoch moves: a refused call leaves this rank's epoch in step
+        check(self.lib.mp4x_ipc_fp8_alltoall_check(dt, r, self.p, plan.soff, elo, ehi, dst, nbp, out.data_ptr()),
+              "mp4x_ipc_fp8_alltoall")
+        self._fp8_stage(dt, send2d.data_ptr(), n_send, plan.nblk_peer[r], plan.soff, st)
+        edev = self._next_epoch(st)
+        # the grid is the same on every rank: from the matrix's largest segment, capped on a shared GPU
+        blocks = self._blocks_for_waves(plan.steps, send2d.dtype, "fp8a2a") or \
+            max(1, min(occupancy.MAX_BLOCKS, -(-plan.steps // 8)))
+        check(self.lib.mp4x_ipc_fp8_alltoall(dt, self._pp_data[0], self._pp_sig[0], r, self.p, plan.soff, elo, ehi,
+                                             dst, nbp, out.data_ptr(), self.epoch, blocks, edev, st),
+              "mp4x_ipc_fp8_alltoall")
         return True
 
     def _blocks_for_waves(self, waves: int, dtype, family: Optional[str] = None) -> int:

@@ -46,7 +46,7 @@ _HOT_MINMAX = {"F32", "BF16", "F16"}
 _FAMILY_KERNEL = {"oneshot": "k_ipc_oneshot", "twoshot": "k_ipc_twoshot", "push": "k_ipc_twoshot_push",
                   "rs": "k_ipc_reduce_range", "gather": "k_ipc_gather", "plan": "k_ipc_copy_plan",
                   "fp8": "k_ipc_fp8_twoshot", "fp8n": "k_ipc_fp8_twoshot_narrow",
-                  "fp8rs": "k_ipc_fp8_rs", "fp8ag": "k_ipc_fp8_ag"}
+                  "fp8rs": "k_ipc_fp8_rs", "fp8ag": "k_ipc_fp8_ag", "fp8a2a": "k_ipc_fp8_a2a"}
 
 
 def kernel_op(dtype_name: str, op_code: int) -> int:

@@ -920,16 +920,31 @@ class ProcessCommSlave:
         from .sparse import broadcast_sparse
         return broadcast_sparse(self.device, keys, vals, rootRank)
 
-    def alltoallArray(self, sendData, sendCounts: Sequence[int], recvData=None):
+    def alltoallArray(self, sendData, sendCounts: Sequence[int], recvData=None, operand: Optional[Operand] = None):
         """Ragged all-to-all of a device tensor (extension; the exchange behind the sparse map
         collectives, exposed for expert-parallel style routing).  ``sendData`` rows are grouped
         by destination rank with ``sendCounts[j]`` rows for rank j.  Returns ``(recv, recvCounts)``
-        with rows grouped by source rank (RCCL all-to-all, every link at once)."""
+        with rows grouped by source rank.  On the GPU mesh, rows of whole 16-byte vectors move in
+        one IPC copy-plan kernel (every rank pulls its block from every peer at once); other
+        widths, and tensors without a mesh, go through the backend's all-to-all.
+
+        ``operand`` (optional) with ``codec="fp8"``: block-scaled e4m3 on the links, for a GPU
+        tensor of f32 / bf16 / f16 (the tensor's dtype decides) whose rows are a multiple of 4
+        elements and whose largest per-rank send, quantised, fits one IPC staging buffer.  Each
+        rank quantises its whole send buffer once, flattened, on ONE grid of 256-element blocks
+        counted from the buffer's first element; a receiver decodes the blocks that touch its rows
+        and stores them with one rounding.  When the row width is a multiple of 256 every row has
+        scales of its own; otherwise blocks straddle rows (and destinations), and a row's decoded
+        values depend on its neighbours in the block — the trade the fp8 reduce-scatter makes.
+        ``recvCounts`` is what the exact call returns.  Where the form does not apply (one rank, a
+        host tensor, a capture, ``MP4X_FP8_TRANSPORT=rccl``, another dtype or width, a send too
+        large for the buffer) the call is the exact all-to-all.  Opt-in only; not measured over
+        real xGMI links."""
         self._tick("alltoallArray")
         self._check_len(sendCounts, "sendCounts")
         if not _is_torch(sendData):
             raise Mp4jException("alltoallArray needs a torch tensor (device engine)")
-        return self.device.all_to_all_v(sendData, list(sendCounts), recvData)
+        return self.device.all_to_all_v(sendData, list(sendCounts), recvData, operand)
 
     # ================================================================ allreduce
     def allreduceArray(self, arrData, operand: Operand, operator, frm: int, to: int, out=None, scale: float = 1.0):
