@@ -166,6 +166,28 @@ int mp4x_dense_reduce_by_key(int dtype, int op, const int64_t* keys, int64_t n, 
                              int64_t base, int64_t stride, int64_t T, void* scratch, size_t scratch_bytes,
                              int64_t* out_keys, void* out_vals, int32_t* out_count, int64_t* m_flag, void* stream);
 
+// ---------------------------------------------------------------- K9 expert-parallel token routing
+// Assignments are flattened token-major (a = t * K + k, n = T * K <= INT32_MAX / 2); the bucket of
+// an assignment is its expert id (int32 or int64 by ids_are_i64), 0 <= id < nb <= 2048.  A negative
+// id and an id >= nb are placed nowhere.  dtype: f32 / bf16 / f16 (else MP4X_E_UNSUPPORTED); a bad
+// pointer, alignment or size is MP4X_E_BADARG before any launch.  Deterministic: no global atomics.
+// Route in two halves with the same scratch (256-byte aligned, scratch_bytes(n, nb)) between them:
+// count -> counts[nb + 2] = assignments per expert | negative ids | ids >= nb (zeros when n == 0).
+size_t mp4x_moe_route_scratch_bytes(int64_t n, int nb);
+int mp4x_moe_route_count(const void* ids, int ids_are_i64, int64_t n, int nb, int64_t* counts, void* scratch,
+                         size_t scratch_bytes, void* stream);
+// scatter -> slots[a] = the position of assignment a in the stable sort by id (-1: placed nowhere);
+// out_rows[slots[a]] = x[a / K] (rows of row_bytes, whole 16-byte vectors, 16-byte aligned), or with
+// row_scale (f32[n]) round_to_dtype(row_scale[a] * f32(x[a / K])): one multiply, one rounding.
+int mp4x_moe_route_scatter(int dtype, const void* ids, int ids_are_i64, const void* x, const float* row_scale,
+                           int64_t n, int K, int64_t row_bytes, int nb, void* out_rows, int64_t* slots,
+                           void* scratch, size_t scratch_bytes, void* stream);
+// Combine: out[t] = round_to_dtype(acc), acc = +0.0f, then for k = 0 .. K-1 with slots[t*K+k] >= 0:
+// acc = acc + w * f32(rows[slots[t*K+k]]), the product and the sum rounded separately (never an
+// FMA), w = weights ? weights[t*K+k] : 1.  Rows of `width` elements, whole 16-byte vectors.
+int mp4x_moe_combine(int dtype, const void* rows, const int64_t* slots, const float* weights, int64_t T, int K,
+                     int64_t width, void* out, void* stream);
+
 // ---------------------------------------------------------------- errors
 // Reads and clears this thread's last HIP error.  mp4x reports its own failures through return
 // codes; a failed HIP call must not stay "last error" for PyTorch's next kernel-launch check to

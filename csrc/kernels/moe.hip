@@ -1,0 +1,322 @@
+// K9 — expert-parallel token routing on the GPU (gfx950): the kernels around the ragged
+// all-to-all of a mixture-of-experts layer.
+//
+// Assignments are flattened token-major: a = t * K + k, n = T * K; the bucket of an assignment
+// is its expert id itself (0 <= id < nb, nb <= 2048).  A negative id and an id >= nb are placed
+// nowhere; they are counted in two buckets of their own behind the experts, so the same scan
+// serves them and they never move an expert's base.
+//
+//   route count    k_moe_hist     per-256-assignment tile LDS histogram -> hist[b * nblk + tile]
+//                  DeviceScan     exclusive sum over (bucket-major, tile-minor)
+//                  k_moe_counts   counts[nb + 2] from the scanned bases
+//   route scatter  k_moe_scatter  K4b's ballot ranks (csrc/kernels/sparse.hip k_pack_scatter):
+//                  slots[a] = base(bucket, tile) + rank inside the tile, staged in LDS, then lane
+//                  groups replicate token rows (16-B loads) into their slots (nontemporal stores),
+//                  optionally scaled per assignment (one multiply per element, one rounding);
+//                  up to 16 blocks share a tile of long rows (tile_split)
+//   combine        k_moe_combine  out[t] = sum over k, in k order, of w[t, k] * rows[slots[t, k]]:
+//                  a lane group per token reads its K rows through the slot index; the mul and
+//                  the add are separate roundings (no contraction), one rounding to the dtype
+//
+// The slot order is exactly the stable sort by expert id.  No global atomics anywhere: every
+// result is identical run to run.
+#include <rocprim/device/device_scan.hpp>
+
+#include "common.hpp"
+
+namespace mp4x {
+
+constexpr int kMoeMaxNb = 2048;      // K4b's kPackMaxP: 4 * nb * 4 B + 2 KiB of LDS in the scatter
+
+__device__ __forceinline__ int64_t moe_id(const void* __restrict__ ids, int is_i64, int64_t i) {
+  return is_i64 ? reinterpret_cast<const int64_t*>(ids)[i] : (int64_t)reinterpret_cast<const int32_t*>(ids)[i];
+}
+
+// acc + w * x with the product and the sum rounded separately, as the eager CPU reference does.
+// hipcc contracts device code by default (and __fmul_rn / __fadd_rn are a plain * and + to it), so
+// contraction is switched off here, where the pragma is honoured.
+__device__ __forceinline__ float mul_rn(float w, float x) {
+#pragma clang fp contract(off)
+  return w * x;
+}
+__device__ __forceinline__ float mul_add_rn(float acc, float w, float x) {
+#pragma clang fp contract(off)
+  const float prod = w * x;
+  return acc + prod;
+}
+
+// Histogram bucket: the expert, or nb (negative: dropped by the caller) / nb + 1 (out of range).
+__device__ __forceinline__ int moe_bucket(int64_t id, int nb) { return id < 0 ? nb : (id >= nb ? nb + 1 : (int)id); }
+
+__global__ __launch_bounds__(kBlock) void k_moe_hist(const void* __restrict__ ids, int is_i64, int64_t n, int nb,
+                                                     int64_t nblk, int64_t* __restrict__ hist) {
+  extern __shared__ __attribute__((aligned(16))) int32_t lh[];
+  const int nbk = nb + 2;
+  for (int i = threadIdx.x; i < nbk; i += kBlock) lh[i] = 0;
+  __syncthreads();
+  const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (i < n) atomicAdd(&lh[moe_bucket(moe_id(ids, is_i64, i), nb)], 1);
+  __syncthreads();
+  for (int d = threadIdx.x; d < nbk; d += kBlock) hist[(int64_t)d * nblk + blockIdx.x] = lh[d];
+}
+
+// One block: counts[q] = assignments of bucket q from the scanned (bucket, tile) bases.
+__global__ __launch_bounds__(kBlock) void k_moe_counts(const int64_t* __restrict__ off, const int64_t* __restrict__ hist,
+                                                       int nbk, int64_t nblk, int64_t* __restrict__ counts) {
+  const int64_t last = (int64_t)nbk * nblk - 1;
+  for (int q = threadIdx.x; q < nbk; q += kBlock) {
+    const int64_t end = (q + 1 < nbk) ? off[(int64_t)(q + 1) * nblk] : off[last] + hist[last];
+    counts[q] = end - off[(int64_t)q * nblk];
+  }
+}
+
+template <int DT, bool SCALED>
+__global__ __launch_bounds__(kBlock) void k_moe_scatter(const void* __restrict__ ids, int is_i64,
+                                                        const u32x4* __restrict__ x,
+                                                        const float* __restrict__ row_scale, int64_t n, int K,
+                                                        int64_t V, int G, int nb, int64_t nblk, int S,
+                                                        const int64_t* __restrict__ off,
+                                                        u32x4* __restrict__ out_rows, int64_t* __restrict__ slots) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  int32_t* wcnt = reinterpret_cast<int32_t*>(smem);                            // [4][nb]
+  int64_t* pos = reinterpret_cast<int64_t*>(smem + ((4 * nb * 4 + 15) & ~15));   // [kBlock]
+  const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63;
+  // S blocks share a tile: each ranks the tile's 256 ids again (cheap) and moves every S-th
+  // group of its rows, so few tiles of long rows still fill the device
+  const int64_t b = blockIdx.x / S, t0 = b * kBlock, i = t0 + tid;
+  const int part = blockIdx.x % S;
+  for (int j = tid; j < 4 * nb; j += kBlock) wcnt[j] = 0;
+  __syncthreads();
+  const int64_t id = i < n ? moe_id(ids, is_i64, i) : -1;
+  const bool placed = id >= 0 && id < nb;
+  const int d = placed ? (int)id : -1;
+  uint64_t active = __ballot(placed);
+  int rank = 0;
+  while (active) {                       // wave-uniform: one trip per distinct expert in the wave
+    const int leader = __ffsll((unsigned long long)active) - 1;
+    const int ld = __shfl(d, leader);
+    const uint64_t m = __ballot(d == ld) & active;
+    if (d == ld) rank = __popcll(m & ((1ull << lane) - 1));
+    if (lane == leader) wcnt[w * nb + ld] = __popcll(m);
+    active &= ~m;
+  }
+  __syncthreads();
+  int64_t ps = -1;
+  if (placed) {
+    int inb = rank;
+    for (int q = 0; q < w; ++q) inb += wcnt[q * nb + d];
+    ps = off[(int64_t)d * nblk + b] + inb;
+    MP4X_DASSERT(ps >= 0 && ps < n);
+  }
+  if (i < n && part == 0) slots[i] = ps;
+  pos[tid] = ps;
+  __syncthreads();
+  const int64_t rows = (n - t0) < kBlock ? (n - t0) : kBlock;
+  const int grp = lane / G, sub = lane % G, R = 64 / G;
+  constexpr int UNR = 4;
+  int it = 0;
+  for (int r0 = w * R + grp; r0 < rows; r0 += 4 * R * UNR, ++it) {
+    if (it % S != part) continue;
+    for (int64_t v = sub; v < V; v += G) {
+      u32x4 y[UNR];
+      int64_t dst[UNR];
+#pragma unroll
+      for (int u = 0; u < UNR; ++u) {
+        const int r = r0 + u * 4 * R;
+        dst[u] = r < rows ? pos[r] : -1;
+        // the K assignments of a token sit next to each other in the tile: its row is read from
+        // memory once and from the cache K - 1 times, so the loads stay temporal
+        // (n <= INT32_MAX / 2: the token index is a 32-bit division)
+        if (dst[u] >= 0) y[u] = x[(int64_t)((uint32_t)(t0 + r) / (uint32_t)K) * V + v];
+      }
+#pragma unroll
+      for (int u = 0; u < UNR; ++u) {
+        if (dst[u] < 0) continue;
+        if constexpr (SCALED) {
+          constexpr int W = 16 / sizeof(typename Elem<DT>::S);
+          const float s = row_scale[t0 + r0 + u * 4 * R];
+          float a[W];
+          unpack<DT>(y[u], a);
+#pragma unroll
+          for (int j = 0; j < W; ++j) a[j] = mul_rn(s, a[j]);
+          y[u] = pack<DT, u32x4>(a);
+        }
+        __builtin_nontemporal_store(y[u], out_rows + dst[u] * V + v);
+      }
+    }
+  }
+}
+
+// G lanes per token (64 / G tokens per wave); a lane owns the 16-byte vectors sub, sub + G, ... of
+// the row and walks the token's K slots in k order.
+template <int DT>
+__global__ __launch_bounds__(kBlock) void k_moe_combine(const u32x4* __restrict__ rows,
+                                                        const int64_t* __restrict__ slots,
+                                                        const float* __restrict__ weights, int64_t T, int K,
+                                                        int64_t V, int G, u32x4* __restrict__ out) {
+  constexpr int W = 16 / sizeof(typename Elem<DT>::S);
+  const int lane = threadIdx.x & 63;
+  const int grp = lane / G, sub = lane % G, R = 64 / G;
+  const int64_t wave = wave_id();
+  const int64_t nwaves = ((int64_t)gridDim.x * kBlock) >> 6;
+  for (int64_t t = wave * R + grp; t < T; t += nwaves * R) {
+    const int64_t* sl = slots + t * K;
+    const float* wt = weights ? weights + t * K : nullptr;
+    for (int64_t v = sub; v < V; v += G) {
+      float acc[W];
+#pragma unroll
+      for (int j = 0; j < W; ++j) acc[j] = 0.0f;
+      for (int k = 0; k < K; ++k) {
+        const int64_t s = sl[k];
+        if (s < 0) continue;
+        MP4X_DASSERT(s < T * K);
+        const float wk = wt ? wt[k] : 1.0f;
+        float a[W];
+        unpack<DT>(rows[s * V + v], a);
+#pragma unroll
+        for (int j = 0; j < W; ++j) acc[j] = mul_add_rn(acc[j], wk, a[j]);
+      }
+      out[t * V + v] = pack<DT, u32x4>(acc);
+    }
+  }
+}
+
+}  // namespace mp4x
+
+using namespace mp4x;
+
+namespace {
+size_t moe_align(size_t x) { return (x + 255) & ~(size_t)255; }
+
+struct MoeScratch {
+  int64_t nblk, m;
+  int64_t *hist, *off;
+  void* temp;
+  size_t temp_bytes;
+};
+
+MoeScratch moe_scratch(void* scratch, size_t scratch_bytes, int64_t n, int nb) {
+  MoeScratch S;
+  S.nblk = (n + kBlock - 1) / kBlock;
+  S.m = (int64_t)(nb + 2) * S.nblk;
+  char* sc = (char*)scratch;
+  const size_t head = 2 * moe_align(S.m * sizeof(int64_t));
+  S.hist = (int64_t*)sc;
+  S.off = (int64_t*)(sc + head / 2);
+  S.temp = sc + head;
+  S.temp_bytes = scratch_bytes - head;
+  return S;
+}
+
+// f32 / bf16 / f16 are the routed dtypes: 0, else MP4X_E_UNSUPPORTED.
+int moe_dtype_ok(int dtype) { return (dtype == MP4X_F32 || dtype == MP4X_BF16 || dtype == MP4X_F16) ? 0 : MP4X_E_UNSUPPORTED; }
+
+int lane_group(int64_t V) {
+  int G = 1;
+  while (G < V && G < 64) G <<= 1;
+  return G;
+}
+
+// Blocks per tile of the scatter: towards 4 blocks per CU (1024) when the tiles alone are fewer,
+// while every block still moves at least 2048 vectors (32 KiB); never more than the 256 / (16 *
+// 64 / G) row groups of a tile (V / 8 <= G / 4 for every V), at most 16.
+int tile_split(int64_t nblk, int64_t V) {
+  int64_t s = 1024 / nblk;
+  if (s > V / 8) s = V / 8;
+  return (int)(s < 1 ? 1 : (s > 16 ? 16 : s));
+}
+}  // namespace
+
+extern "C" size_t mp4x_moe_route_scratch_bytes(int64_t n, int nb) {
+  const int64_t nblk = (n + kBlock - 1) / kBlock;
+  const int64_t m = (int64_t)(nb + 2) * (nblk < 1 ? 1 : nblk);
+  size_t cub_bytes = 0;
+  (void)rocprim::exclusive_scan(nullptr, cub_bytes, (const int64_t*)nullptr, (int64_t*)nullptr, (int64_t)0, (size_t)m,
+                                rocprim::plus<int64_t>(), (hipStream_t)0);
+  return 2 * moe_align(m * sizeof(int64_t)) + moe_align(cub_bytes);
+}
+
+extern "C" int mp4x_moe_route_count(const void* ids, int ids_are_i64, int64_t n, int nb, int64_t* counts,
+                                    void* scratch, size_t scratch_bytes, void* stream) {
+  hipStream_t st = (hipStream_t)stream;
+  if (nb < 1 || nb > kMoeMaxNb || n < 0 || !counts || ((uintptr_t)counts & 7)) return MP4X_E_BADARG;
+  if (n == 0) return (int)hipMemsetAsync(counts, 0, (nb + 2) * sizeof(int64_t), st);
+  if (n > INT32_MAX / 2 || !ids || ((uintptr_t)ids & (ids_are_i64 ? 7 : 3)) || !scratch || ((uintptr_t)scratch & 255))
+    return MP4X_E_BADARG;
+  if (scratch_bytes < mp4x_moe_route_scratch_bytes(n, nb)) return MP4X_E_BADARG;
+  MoeScratch S = moe_scratch(scratch, scratch_bytes, n, nb);
+  hipLaunchKernelGGL(k_moe_hist, dim3(S.nblk), dim3(kBlock), (nb + 2) * sizeof(int32_t), st, ids, ids_are_i64, n, nb,
+                     S.nblk, S.hist);
+  int e = (int)hipGetLastError();
+  if (e) return e;
+  e = (int)rocprim::exclusive_scan(S.temp, S.temp_bytes, S.hist, S.off, (int64_t)0, (size_t)S.m,
+                                   rocprim::plus<int64_t>(), st);
+  if (e) return e;
+  hipLaunchKernelGGL(k_moe_counts, dim3(1), dim3(kBlock), 0, st, (const int64_t*)S.off, (const int64_t*)S.hist, nb + 2,
+                     S.nblk, counts);
+  return (int)hipGetLastError();
+}
+
+extern "C" int mp4x_moe_route_scatter(int dtype, const void* ids, int ids_are_i64, const void* x,
+                                      const float* row_scale, int64_t n, int K, int64_t row_bytes, int nb,
+                                      void* out_rows, int64_t* slots, void* scratch, size_t scratch_bytes,
+                                      void* stream) {
+  if (int e = moe_dtype_ok(dtype)) return e;
+  if (nb < 1 || nb > kMoeMaxNb || n < 0 || K < 1 || n % K || row_bytes < 16 || (row_bytes & 15)) return MP4X_E_BADARG;
+  if (n == 0) return 0;
+  if (n > INT32_MAX / 2 || !ids || ((uintptr_t)ids & (ids_are_i64 ? 7 : 3)) || !x || !out_rows ||
+      (((uintptr_t)x | (uintptr_t)out_rows) & 15) || !slots || ((uintptr_t)slots & 7) || ((uintptr_t)row_scale & 3) ||
+      !scratch || ((uintptr_t)scratch & 255))
+    return MP4X_E_BADARG;
+  if (scratch_bytes < mp4x_moe_route_scratch_bytes(n, nb)) return MP4X_E_BADARG;
+  const MoeScratch S_ = moe_scratch(scratch, scratch_bytes, n, nb);
+  const int64_t V = row_bytes / 16;
+  const int G = lane_group(V);
+  const size_t lds = ((4 * nb * 4 + 15) & ~15) + kBlock * sizeof(int64_t);
+  const int S = tile_split(S_.nblk, V);
+  hipStream_t st = (hipStream_t)stream;
+  if (!row_scale) {                      // whole rows move as bytes: one instantiation serves every dtype
+    hipLaunchKernelGGL((k_moe_scatter<MP4X_F32, false>), dim3(S_.nblk * S), dim3(kBlock), lds, st, ids, ids_are_i64,
+                       (const u32x4*)x, row_scale, n, K, V, G, nb, S_.nblk, S, (const int64_t*)S_.off, (u32x4*)out_rows,
+                       slots);
+    return (int)hipGetLastError();
+  }
+  return with_dtype(dtype, [&](auto dtc) {
+    constexpr int DT = decltype(dtc)::value;
+    if constexpr (DT == MP4X_F32 || DT == MP4X_BF16 || DT == MP4X_F16) {
+      hipLaunchKernelGGL((k_moe_scatter<DT, true>), dim3(S_.nblk * S), dim3(kBlock), lds, st, ids, ids_are_i64,
+                         (const u32x4*)x, row_scale, n, K, V, G, nb, S_.nblk, S, (const int64_t*)S_.off,
+                         (u32x4*)out_rows, slots);
+      return (int)hipGetLastError();
+    } else {
+      return (int)MP4X_E_UNSUPPORTED;
+    }
+  });
+}
+
+extern "C" int mp4x_moe_combine(int dtype, const void* rows, const int64_t* slots, const float* weights, int64_t T,
+                                int K, int64_t width, void* out, void* stream) {
+  if (int e = moe_dtype_ok(dtype)) return e;
+  const int64_t row_bytes = width * elem_size(dtype);
+  if (T < 0 || K < 1 || width < 1 || (row_bytes & 15)) return MP4X_E_BADARG;
+  if (T == 0) return 0;
+  // rows may be NULL only when nothing was placed, which the kernel cannot know: the caller passes
+  // a valid (possibly one-row) buffer
+  if (T > INT32_MAX / 2 / K || !rows || !out || (((uintptr_t)rows | (uintptr_t)out) & 15) || !slots ||
+      ((uintptr_t)slots & 7) || ((uintptr_t)weights & 3))
+    return MP4X_E_BADARG;
+  const int64_t V = row_bytes / 16;
+  const int G = lane_group(V);
+  const int g = grid_for((T * G + 63) / 64 * 64, 1);
+  hipStream_t st = (hipStream_t)stream;
+  return with_dtype(dtype, [&](auto dtc) {
+    constexpr int DT = decltype(dtc)::value;
+    if constexpr (DT == MP4X_F32 || DT == MP4X_BF16 || DT == MP4X_F16) {
+      hipLaunchKernelGGL((k_moe_combine<DT>), dim3(g), dim3(kBlock), 0, st, (const u32x4*)rows, slots, weights, T, K, V,
+                         G, (u32x4*)out);
+      return (int)hipGetLastError();
+    } else {
+      return (int)MP4X_E_UNSUPPORTED;
+    }
+  });
+}

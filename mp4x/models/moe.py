@@ -1,0 +1,153 @@
+"""Expert-parallel mixture-of-experts layer on ``dispatchTokens`` / ``combineTokens``.
+
+Rank ``r`` of ``p`` holds experts ``[r*E/p, (r+1)*E/p)``; every rank routes its own tokens.  The
+two collectives are differentiable here:
+
+* :func:`dispatch_tokens` — backward is a combine with unit weights on the return path: the
+  gradient of token t is the sum, in k order, of the gradients of its K dispatched rows;
+* :func:`combine_tokens` — backward w.r.t. the expert rows is a dispatch of the output gradient
+  along the same plan with every assignment's row scaled by its gate weight (the K9 route scatter
+  with ``row_scale``; the plan's count matrix, no new count exchange); backward w.r.t. the weights
+  is the row dot ``sum_h g[t, h] * y[slot(t, k), h]`` in torch (not a hot path here).
+
+Both backward passes are collectives: every rank must run them, in the same order, which autograd
+does for the same graph on every rank.
+
+:class:`ExpertParallelMoE` is the layer: router linear -> softmax -> top-k -> dispatch -> each
+local expert's two-layer MLP on its ``expert_counts`` slice -> combine with the gate weights.
+"""
+from __future__ import annotations
+
+from typing import Dict, Optional
+
+import torch
+
+from ..operands import Operands
+from ..operators import Operators
+
+
+class _Dispatch(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, comm, expert_ids, num_experts, operand):
+        rows, plan = comm.dispatchTokens(x.contiguous(), expert_ids, num_experts, operand=operand)
+        ctx.comm, ctx.plan, ctx.operand = comm, plan, operand
+        return rows, plan
+
+    @staticmethod
+    def backward(ctx, g_rows, _plan=None):
+        gx = ctx.comm.combineTokens(g_rows.contiguous(), ctx.plan, None, operand=ctx.operand)
+        return gx, None, None, None, None
+
+
+class _Combine(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, rows, weights, comm, plan, operand):
+        out, back = comm.combineTokens(rows.contiguous(), plan, weights, operand=operand, returnSlotRows=True)
+        ctx.comm, ctx.plan, ctx.operand = comm, plan, operand
+        ctx.save_for_backward(back, weights)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        back, weights = ctx.saved_tensors
+        plan = ctx.plan
+        g = g.contiguous()
+        g_rows, _ = ctx.comm.device.dispatch_tokens(g, None, plan.num_experts, ctx.operand, plan=plan,
+                                                    row_scale=weights)
+        g_w = None
+        if weights is not None and ctx.needs_input_grad[1]:
+            T, K = plan.num_tokens, plan.top_k
+            sl = plan.slots.view(T, K)
+            if back.shape[0]:
+                y = back.reshape(back.shape[0], -1)[sl.clamp(min=0)].to(torch.float32)      # [T, K, H]
+                g_w = (g.reshape(T, 1, -1).to(torch.float32) * y).sum(-1)
+                g_w = torch.where(sl >= 0, g_w, torch.zeros_like(g_w)).view_as(weights)
+            else:
+                g_w = torch.zeros_like(weights)
+        return g_rows, g_w, None, None, None
+
+
+def dispatch_tokens(comm, x: torch.Tensor, expert_ids: torch.Tensor, num_experts: int, operand=None):
+    """Differentiable ``comm.dispatchTokens``: ``(rows, plan)``."""
+    return _Dispatch.apply(x, comm, expert_ids, num_experts, operand)
+
+
+def combine_tokens(comm, expert_rows: torch.Tensor, plan, weights: Optional[torch.Tensor] = None, operand=None):
+    """Differentiable ``comm.combineTokens`` (w.r.t. the rows and the weights)."""
+    return _Combine.apply(expert_rows, weights, comm, plan, operand)
+
+
+class ExpertParallelMoE(torch.nn.Module):
+    """Top-k routed mixture of two-layer ReLU MLP experts, experts sharded over the ranks.
+
+    The full parameter set is drawn from ``seed`` on every rank (:meth:`init_weights`) and this rank
+    keeps the router (replicated) and its own experts' slices, so a single-process model built from
+    the same seed holds exactly the same weights.  After ``backward`` call :meth:`sync_gradients`:
+    for a loss that is the mean over ranks of per-rank losses it averages the router's gradient
+    over the ranks and scales the experts' (already summed over every rank's tokens by the
+    combine / dispatch backward) by ``1/p``."""
+
+    def __init__(self, comm, d_model: int, d_hidden: int, num_experts: int, top_k: int, seed: int = 0,
+                 device=None, dtype=torch.float32, operand=None):
+        super().__init__()
+        p, r = comm.getSlaveNum(), comm.getRank()
+        if num_experts % p:
+            raise ValueError(f"num_experts {num_experts} is not a multiple of the {p} ranks")
+        if not 1 <= top_k <= num_experts:
+            raise ValueError("top_k must be in [1, num_experts]")
+        self.comm, self.num_experts, self.top_k, self.operand = comm, num_experts, top_k, operand
+        self.local_experts = num_experts // p
+        self.first_expert = r * self.local_experts
+        full = self.init_weights(d_model, d_hidden, num_experts, seed)
+        lo, hi = self.first_expert, self.first_expert + self.local_experts
+
+        def par(t):
+            return torch.nn.Parameter(t.to(device=device, dtype=dtype).contiguous())
+        self.router = par(full["router"])
+        self.w1, self.b1 = par(full["w1"][lo:hi]), par(full["b1"][lo:hi])
+        self.w2, self.b2 = par(full["w2"][lo:hi]), par(full["b2"][lo:hi])
+
+    @staticmethod
+    def init_weights(d_model: int, d_hidden: int, num_experts: int, seed: int = 0) -> Dict[str, torch.Tensor]:
+        """The whole model's weights (float32, CPU): router [d_model, E], w1 [E, d_model, d_hidden],
+        b1 [E, d_hidden], w2 [E, d_hidden, d_model], b2 [E, d_model]."""
+        g = torch.Generator().manual_seed(seed)
+
+        def rnd(*shape, fan_in):
+            return (torch.rand(*shape, generator=g) * 2 - 1) / fan_in ** 0.5
+        return {"router": rnd(d_model, num_experts, fan_in=d_model),
+                "w1": rnd(num_experts, d_model, d_hidden, fan_in=d_model),
+                "b1": rnd(num_experts, d_hidden, fan_in=d_model),
+                "w2": rnd(num_experts, d_hidden, d_model, fan_in=d_hidden),
+                "b2": rnd(num_experts, d_model, fan_in=d_hidden)}
+
+    def route(self, x: torch.Tensor):
+        """(gate weights float32 [T, K], expert ids int64 [T, K]): softmax over the router's logits,
+        top-k, the k-th largest first."""
+        probs = torch.softmax((x @ self.router).to(torch.float32), dim=-1)
+        return torch.topk(probs, self.top_k, dim=-1)
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        w, ids = self.route(x)
+        rows, plan = dispatch_tokens(self.comm, x, ids, self.num_experts, self.operand)
+        outs, off = [], 0
+        for e, c in enumerate(plan.expert_counts):
+            h = torch.relu(rows[off:off + c] @ self.w1[e] + self.b1[e])
+            outs.append(h @ self.w2[e] + self.b2[e])
+            off += c
+        y = torch.cat(outs) if outs else rows
+        return combine_tokens(self.comm, y, plan, w.contiguous(), self.operand)
+
+    def sync_gradients(self) -> None:
+        p = self.comm.getSlaveNum()
+        if p == 1:
+            return
+        for q in (self.w1, self.b1, self.w2, self.b2):
+            if q.grad is not None:
+                q.grad.mul_(1.0 / p)
+        g = self.router.grad if self.router.grad is not None else torch.zeros_like(self.router)
+        flat = g.contiguous().view(-1)
+        operand = {torch.float32: Operands.FLOAT_OPERAND, torch.bfloat16: Operands.BF16_OPERAND,
+                   torch.float16: Operands.HALF_OPERAND}[flat.dtype]()
+        self.comm.allreduceArray(flat, operand, Operators.Float.SUM, 0, flat.numel(), scale=1.0 / p)
+        self.router.grad = flat.view_as(self.router)

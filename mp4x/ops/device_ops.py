@@ -431,6 +431,121 @@ def partition_scatter(pc: PackCount, vals: Optional[torch.Tensor], out_vals_ptr:
           "mp4x_partition_pack_scatter")
 
 
+# ------------------------------------------------------------------ K9 expert-parallel token routing
+MOE_MAX_EXPERTS = 2048
+MOE_DTYPES = (torch.float32, torch.bfloat16, torch.float16)
+
+
+class RouteCount(NamedTuple):
+    """The first half of K9's route (:func:`moe_route_count`): ``counts`` = assignments per expert
+    [nb] + [negative ids, ids >= nb]; ``scratch`` holds the scan :func:`moe_route_scatter` reads."""
+    ids: torch.Tensor
+    nb: int
+    counts: torch.Tensor
+    scratch: torch.Tensor
+
+
+def _moe_rows(fn: str, rows: torch.Tensor) -> Tuple[int, int]:
+    """(elements, bytes) of one row of ``rows`` [R, ...]: f32 / bf16 / f16, whole 16-byte vectors."""
+    if rows.dtype not in MOE_DTYPES:
+        raise ValueError(f"{fn}: dtype {rows.dtype} is not float32 / bfloat16 / float16")
+    width = 1
+    for d in rows.shape[1:]:
+        width *= int(d)
+    rb = width * rows.element_size()
+    if rows.dim() < 1 or rb == 0 or rb % 16:
+        raise ValueError(f"{fn}: rows of {rb} bytes are not whole 16-byte vectors")
+    return width, rb
+
+
+def moe_route_count(ids: torch.Tensor, nb: int, stream=None) -> RouteCount:
+    """K9's histogram + scan over the flattened (token, k) expert ids (int32 / int64): rows per
+    expert ``0 <= id < nb`` and the number of negative and of too-large ids, with no rows moved
+    yet (the caller can exchange the counts first)."""
+    _dev_check(ids)
+    if ids.dtype not in (torch.int32, torch.int64):
+        raise ValueError("moe_route_count: ids must be int32 or int64")
+    if not 1 <= nb <= MOE_MAX_EXPERTS:
+        raise ValueError(f"moe_route_count: nb must be in [1, {MOE_MAX_EXPERTS}]")
+    n = ids.numel()
+    lib = native.hip()
+    sb = lib.mp4x_moe_route_scratch_bytes(n, nb)
+    scratch = torch.empty(max(sb, 1), dtype=torch.uint8, device=ids.device)
+    counts = torch.empty(nb + 2, dtype=torch.int64, device=ids.device)
+    check(lib.mp4x_moe_route_count(ids.data_ptr(), int(ids.dtype == torch.int64), n, nb, counts.data_ptr(),
+                                   scratch.data_ptr(), sb, stream_ptr(stream)), "mp4x_moe_route_count")
+    return RouteCount(ids, nb, counts, scratch)
+
+
+def moe_route_scatter(rc: RouteCount, x: torch.Tensor, top_k: int, out_rows: torch.Tensor,
+                      row_scale: Optional[torch.Tensor] = None, placed: Optional[int] = None,
+                      stream=None) -> torch.Tensor:
+    """K9's scatter after :func:`moe_route_count`: ``slots`` int64[n], the position of assignment
+    ``a = t * top_k + k`` in the stable sort by expert id (-1 where it is placed nowhere), and
+    ``out_rows[slots[a]] = x[t]``, times ``row_scale[a]`` (float32, one rounding) when given.
+    ``out_rows`` must hold every placed assignment (``rc.counts[:nb].sum()`` rows)."""
+    ids = rc.ids
+    n = ids.numel()
+    _dev_check(ids, x, out_rows, row_scale)
+    _, rb = _moe_rows("moe_route_scatter", x)
+    if top_k < 1 or x.shape[0] * top_k != n:
+        raise ValueError(f"moe_route_scatter: {x.shape[0]} rows x top_k {top_k} != {n} ids")
+    if out_rows.dtype != x.dtype or tuple(out_rows.shape[1:]) != tuple(x.shape[1:]):
+        raise ValueError("moe_route_scatter: out_rows dtype / row shape differ from x")
+    if row_scale is not None and (row_scale.dtype != torch.float32 or row_scale.numel() != n):
+        raise ValueError("moe_route_scatter: row_scale must be float32, one per assignment")
+    slots = torch.empty(n, dtype=torch.int64, device=ids.device)
+    if n == 0:
+        return slots
+    # every computed slot is below the number of placed assignments (<= n): out_rows must hold
+    # them.  ``placed``: that number when the caller has it on the host already (no sync here).
+    if out_rows.shape[0] < n:
+        if placed is None:
+            placed = int(rc.counts[:rc.nb].sum())
+        if out_rows.shape[0] < placed:
+            raise ValueError("moe_route_scatter: out_rows holds fewer rows than are placed")
+    if out_rows.shape[0] == 0:             # nothing is placed: the kernel still wants a valid address
+        out_rows = torch.empty((1,) + tuple(x.shape[1:]), dtype=x.dtype, device=x.device)
+    check(native.hip().mp4x_moe_route_scatter(int(dtype_of_torch(x.dtype)), ids.data_ptr(),
+                                              int(ids.dtype == torch.int64), x.data_ptr(),
+                                              row_scale.data_ptr() if row_scale is not None else None, n,
+                                              int(top_k), rb, rc.nb, out_rows.data_ptr(), slots.data_ptr(),
+                                              rc.scratch.data_ptr(), rc.scratch.numel(), stream_ptr(stream)),
+          "mp4x_moe_route_scatter")
+    return slots
+
+
+def moe_combine(rows: torch.Tensor, slots: torch.Tensor, weights: Optional[torch.Tensor], num_tokens: int,
+                top_k: int, out: Optional[torch.Tensor] = None, max_slot: Optional[int] = None, stream=None):
+    """K9's combine: ``out[t] = sum over k, in k order, of weights[t, k] * rows[slots[t * top_k + k]]``
+    (f32 accumulate from +0, product and sum rounded separately, slots < 0 skipped, one rounding to
+    ``rows.dtype``).  ``max_slot`` is the largest slot when the caller already knows it (the plan's
+    send total - 1); otherwise it is read back from ``slots`` for the bounds check."""
+    _dev_check(rows, slots, weights, out)
+    width, _ = _moe_rows("moe_combine", rows)
+    n = num_tokens * top_k
+    if slots.dtype != torch.int64 or slots.numel() != n or top_k < 1:
+        raise ValueError("moe_combine: slots must be int64, num_tokens * top_k of them")
+    if weights is not None and (weights.dtype != torch.float32 or weights.numel() != n):
+        raise ValueError("moe_combine: weights must be float32, one per assignment")
+    if out is None:
+        out = torch.empty((num_tokens,) + tuple(rows.shape[1:]), dtype=rows.dtype, device=rows.device)
+    elif out.dtype != rows.dtype or tuple(out.shape) != (num_tokens,) + tuple(rows.shape[1:]):
+        raise ValueError("moe_combine: out dtype / shape mismatch")
+    if n == 0:
+        return out
+    if max_slot is None:
+        max_slot = int(slots.max())
+    if max_slot >= rows.shape[0]:
+        raise ValueError(f"moe_combine: slot {max_slot} past the {rows.shape[0]} rows")
+    # (a call with nothing placed still hands the kernel a readable address)
+    src = rows if rows.shape[0] else torch.zeros((1,) + tuple(rows.shape[1:]), dtype=rows.dtype, device=rows.device)
+    check(native.hip().mp4x_moe_combine(int(dtype_of_torch(rows.dtype)), src.data_ptr(), slots.data_ptr(),
+                                        weights.data_ptr() if weights is not None else None, num_tokens, int(top_k),
+                                        width, out.data_ptr(), stream_ptr(stream)), "mp4x_moe_combine")
+    return out
+
+
 # int64 key sorts: rocPRIM's own dispatch (block sort + merge passes below 1 M items, whatever the
 # key width) or forced onesweep (csrc/kernels/sparse.hip OnesweepSort: ~27 us per 8-bit pass at
 # 200 k items).  Measured on MI355X (profiles/r6/sparse/sort_ab.jsonl): onesweep wins at <= 16 bits

@@ -1573,25 +1573,31 @@ class DeviceEngine(AutotuneMixin, ScheduleMixin, RootedMixin):
         return allreduce_map_device(self, mapData, operator)
 
     def all_to_all_v(self, send: torch.Tensor, send_counts: List[int], recv: Optional[torch.Tensor] = None,
-                     operand=None):
+                     operand=None, mat=None):
         """Ragged all-to-all over rows of ``send`` (rows grouped by destination).  An ``operand``
         with ``codec="fp8"`` asks for e4m3 on the links (:meth:`_all_to_all_v_fp8`); where that
-        form does not apply, and without it, the call is the exact one."""
+        form does not apply, and without it, the call is the exact one.  ``mat`` (optional): the
+        count matrix (``mat[i][j]`` rows from rank i to rank j) when every rank holds it already
+        (the token dispatch): no form then exchanges counts."""
         self._count("all_to_all_v")
         if sum(send_counts) != send.shape[0]:
             raise Mp4jException(f"sendCounts sum {sum(send_counts)} != rows {send.shape[0]}")
-        mat = None
+        if mat is not None and list(mat[self.rank]) != list(send_counts):
+            raise Mp4jException(f"sendCounts {list(send_counts)} != the count matrix's row {list(mat[self.rank])}")
         if getattr(operand, "codec", None) == "fp8":
-            got, mat = self._all_to_all_v_fp8(send, send_counts, recv)
+            got, mat = self._all_to_all_v_fp8(send, send_counts, recv, mat)
             if got is not None:
                 return got
         got = self._all_to_all_v_ipc(send, send_counts, recv, mat)
         if got is not None:
             return got
-        sc = torch.tensor(send_counts, dtype=torch.int64, device=self.device if self.backend == "nccl" else "cpu")
-        rc = torch.empty_like(sc)
-        self.coll.all_to_all_single(rc, sc)
-        recv_counts = [int(x) for x in rc.tolist()]
+        if mat is not None:
+            recv_counts = [int(mat[j][self.rank]) for j in range(self.p)]
+        else:
+            sc = torch.tensor(send_counts, dtype=torch.int64, device=self.device if self.backend == "nccl" else "cpu")
+            rc = torch.empty_like(sc)
+            self.coll.all_to_all_single(rc, sc)
+            recv_counts = [int(x) for x in rc.tolist()]
         shape = (sum(recv_counts),) + tuple(send.shape[1:])
         if recv is None:
             recv = torch.empty(shape, dtype=send.dtype, device=send.device)
@@ -1607,14 +1613,16 @@ class DeviceEngine(AutotuneMixin, ScheduleMixin, RootedMixin):
             width *= int(d)
         return width
 
-    def _all_to_all_v_fp8(self, send: torch.Tensor, send_counts: List[int], recv: Optional[torch.Tensor]):
+    def _all_to_all_v_fp8(self, send: torch.Tensor, send_counts: List[int], recv: Optional[torch.Tensor],
+                          mat=None):
         """The all-to-all-v with the block-scaled e4m3 codec on the links
         (``IpcAllreduce.alltoall_fp8``): a GPU tensor of f32 / bf16 / f16 (the tensor's dtype
         decides, not the operand's) whose rows are a multiple of 4 elements, the IPC mesh of the
         exact form (:meth:`_all_to_all_v_ipc`), ``MP4X_FP8_TRANSPORT`` not ``rccl``, and the
         largest send of any rank, quantised, inside one staging buffer.  Every condition is
         rank-independent.  Returns ``(result or None, count matrix or None)``: a declined call
-        hands the matrix it gathered to the exact form, which then does not gather it again."""
+        hands the matrix it gathered (or was given: ``mat``) to the exact form, which then does not
+        gather it again."""
         from . import sparse
         from .ipc import IpcAllreduce
         width = self._row_width(send)
@@ -1622,8 +1630,9 @@ class DeviceEngine(AutotuneMixin, ScheduleMixin, RootedMixin):
                 or self.algo not in ("", "auto", "ipc") \
                 or os.environ.get("MP4X_FP8_TRANSPORT", "auto").lower() == "rccl" \
                 or not sparse._sparse_ipc_ok(self, send):
-            return None, None
-        mat = sparse._count_matrix(self, torch.tensor(list(send_counts), dtype=torch.int64, device=send.device))
+            return None, mat
+        if mat is None:
+            mat = sparse._count_matrix(self, torch.tensor(list(send_counts), dtype=torch.int64, device=send.device))
         recv_counts = [mat[j][self.rank] for j in range(self.p)]
         shape = (sum(recv_counts),) + tuple(send.shape[1:])
         if recv is not None and tuple(recv.shape) != shape:
@@ -1670,6 +1679,25 @@ class DeviceEngine(AutotuneMixin, ScheduleMixin, RootedMixin):
             recv.copy_(res)
             res = recv
         return res, recv_counts
+
+    # ================================================================== expert-parallel routing
+    def dispatch_tokens(self, x: torch.Tensor, expert_ids: torch.Tensor, num_experts: int, operand=None,
+                        plan=None, row_scale=None):
+        """Token rows to the ranks that own their experts, grouped by local expert
+        (parallel/moe.py).  ``plan`` + ``row_scale``: dispatch again along an earlier plan, rows
+        scaled per assignment (the combine's backward), with no count exchange."""
+        from . import moe
+        self._count("moe.dispatch")
+        if plan is not None:
+            return moe.dispatch_scaled(self, x, plan, row_scale, operand), plan
+        return moe.dispatch(self, x, expert_ids, num_experts, operand)
+
+    def combine_tokens(self, expert_rows: torch.Tensor, plan, weights=None, operand=None, return_slot_rows=False):
+        """Expert rows back to their tokens, every token's K rows summed with its weights in k
+        order (parallel/moe.py)."""
+        from . import moe
+        self._count("moe.combine")
+        return moe.combine(self, expert_rows, plan, weights, operand, return_slot_rows)
 
     def reduce_map(self, mapData: Dict, operator, root: int):
         from .sparse import reduce_map_device
@@ -1770,6 +1798,6 @@ for _n in _TIER_ATTRS:
 _WATCHED = ["allreduce", "autotune_allreduce", "autotune_reduce_scatter", "autotune_allgather", "autotune_reduce",
             "autotune_broadcast", "autotune_gather", "autotune_scatter", "reduce_scatter", "allgather", "broadcast", "reduce", "gather",
             "scatter", "allreduce_map", "all_to_all_v", "reduce_map", "gather_map", "allgather_map",
-            "reduce_scatter_map", "scatter_map", "broadcast_map", "barrier"]
+            "reduce_scatter_map", "scatter_map", "broadcast_map", "barrier", "dispatch_tokens", "combine_tokens"]
 for _n in _WATCHED:
     setattr(DeviceEngine, _n, _watched(_n, getattr(DeviceEngine, _n)))

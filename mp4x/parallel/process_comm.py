@@ -946,6 +946,54 @@ class ProcessCommSlave:
             raise Mp4jException("alltoallArray needs a torch tensor (device engine)")
         return self.device.all_to_all_v(sendData, list(sendCounts), recvData, operand)
 
+    def dispatchTokens(self, x, expertIds, numExperts: int, operand: Optional[Operand] = None):
+        """Expert-parallel token dispatch (extension, over ``alltoallArray``'s transport).
+
+        ``x`` is ``[T, ...]`` (contiguous; f32 / bf16 / f16), ``expertIds`` ``[T, K]`` or ``[T]``
+        (int32 / int64, on ``x``'s device): token t goes to each of its K experts.  Rank r owns
+        experts ``[r*E/p, (r+1)*E/p)`` of ``numExperts = E`` (a multiple of the rank count, at
+        most 2048).  A negative id drops that assignment.  Returns ``(rows, plan)``: ``rows``
+        ``[R, ...]`` are the token rows this rank's experts received, grouped by local expert in
+        ascending order, inside an expert by source rank, inside a source in the sender's token
+        order; ``plan.expert_counts`` holds the group sizes and ``plan`` (a read-only
+        :class:`~mp4x.parallel.moe.TokenPlan`) is what :meth:`combineTokens` needs.
+
+        On a GPU tensor (rows of whole 16-byte vectors) the routing runs in the K9 kernels: a
+        stable LDS multisplit by expert id that replicates rows straight into send order, with
+        no sort and no atomics.  One exchange of ``E + 2`` counts per rank serves the call, the
+        all-to-all inside it and every later combine.  ``operand`` is handed to the all-to-all
+        unchanged (``codec="fp8"``: see :meth:`alltoallArray`).  Host tensors take a torch
+        implementation of the same contract.
+
+        Raises :class:`Mp4jException`, on every rank alike and before any row moves, for ``E``
+        not a multiple of the rank count or above 2048, mismatched shapes, an id ``>= E`` on any
+        rank (the message names the rank), another dtype, GPU rows that are not whole 16-byte
+        vectors, and a call inside a graph capture (the count exchange is a host sync)."""
+        self._tick("dispatchTokens")
+        if not _is_torch(x):
+            raise Mp4jException("dispatchTokens needs a torch tensor (device engine)")
+        return self.device.dispatch_tokens(x, expertIds, numExperts, operand)
+
+    def combineTokens(self, expertRows, plan, weights=None, operand: Optional[Operand] = None,
+                      returnSlotRows: bool = False):
+        """The way back of :meth:`dispatchTokens`: ``expertRows`` ``[R, ...]`` (the experts'
+        outputs, in the layout ``dispatchTokens`` returned) go back to the ranks their tokens
+        came from, and token t's K rows are summed in k order, ``acc = acc + weights[t, k] * row``
+        in f32 (product and sum rounded separately, from +0), then rounded once to
+        ``expertRows``' dtype.  ``weights`` is ``[T, K]`` float32, or None for 1.  Returns
+        ``[T, ...]``; a token with every assignment dropped gets zeros.  No count exchange (the
+        plan's matrix, transposed) and no atomics: the result is identical run to run, and bit for
+        bit the CPU form's.  ``returnSlotRows``: also return the rows as they came back, in the
+        sender's slot order (``plan.slots``), which the weights' gradient needs.
+
+        Raises :class:`Mp4jException` for weights that are not float32 ``[T, K]``, rows that do
+        not match the plan (``expertRows.shape[0] != sum(plan.expert_counts)``, dtype, row shape)
+        and a call inside a graph capture."""
+        self._tick("combineTokens")
+        if not _is_torch(expertRows):
+            raise Mp4jException("combineTokens needs a torch tensor (device engine)")
+        return self.device.combine_tokens(expertRows, plan, weights, operand, returnSlotRows)
+
     # ================================================================ allreduce
     def allreduceArray(self, arrData, operand: Operand, operator, frm: int, to: int, out=None, scale: float = 1.0):
         """reduce-scatter + allgather with the last rank taking the remainder (reference :1733-1763).
