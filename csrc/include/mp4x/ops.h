@@ -182,6 +182,16 @@ int mp4x_moe_route_count(const void* ids, int ids_are_i64, int64_t n, int nb, in
 int mp4x_moe_route_scatter(int dtype, const void* ids, int ids_are_i64, const void* x, const float* row_scale,
                            int64_t n, int K, int64_t row_bytes, int nb, void* out_rows, int64_t* slots,
                            void* scratch, size_t scratch_bytes, void* stream);
+// The scatter under an expert capacity.  clip (int64[2 * nb], 8-byte aligned, device memory):
+// clip[e] = keep[e], the rows of expert e this rank may send; clip[nb + e] = kept_base[e], the
+// exclusive prefix of keep over the experts.  Assignment a with expert e, the pe-th of this rank's
+// assignments with that expert (in a order), gets slots[a] = pe < keep[e] ? kept_base[e] + pe : -1:
+// the stable sort of the kept assignments.  A clipped row is neither read nor written; out_rows
+// holds sum(keep) rows.  keep[e] >= the count of e is the unclipped scatter bit for bit.  A null
+// or misaligned clip is MP4X_E_BADARG, with everything the unclipped entry refuses; n == 0 is 0.
+int mp4x_moe_route_scatter_clip(int dtype, const void* ids, int ids_are_i64, const void* x, const float* row_scale,
+                                int64_t n, int K, int64_t row_bytes, int nb, void* out_rows, int64_t* slots,
+                                const int64_t* clip, void* scratch, size_t scratch_bytes, void* stream);
 // Combine: out[t] = round_to_dtype(acc), acc = +0.0f, then for k = 0 .. K-1 with slots[t*K+k] >= 0:
 // acc = acc + w * f32(rows[slots[t*K+k]]), the product and the sum rounded separately (never an
 // FMA), w = weights ? weights[t*K+k] : 1.  Rows of `width` elements, whole 16-byte vectors.

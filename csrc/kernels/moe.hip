@@ -13,7 +13,9 @@
 //                  slots[a] = base(bucket, tile) + rank inside the tile, staged in LDS, then lane
 //                  groups replicate token rows (16-B loads) into their slots (nontemporal stores),
 //                  optionally scaled per assignment (one multiply per element, one rounding);
-//                  up to 16 blocks share a tile of long rows (tile_split)
+//                  up to 16 blocks share a tile of long rows (tile_split); with an expert
+//                  capacity (CLIP) an assignment past its expert's quota gets slot -1 there and
+//                  its row is neither read nor written
 //   combine        k_moe_combine  out[t] = sum over k, in k order, of w[t, k] * rows[slots[t, k]]:
 //                  a lane group per token reads its K rows through the slot index; the mul and
 //                  the add are separate roundings (no contraction), one rounding to the dtype
@@ -70,12 +72,18 @@ __global__ __launch_bounds__(kBlock) void k_moe_counts(const int64_t* __restrict
   }
 }
 
-template <int DT, bool SCALED>
+// CLIP (an expert capacity): clip[0 .. nb) = keep[e], the rows of expert e this rank may send, and
+// clip[nb .. 2 nb) = kept_base[e], the exclusive prefix of keep.  The position of an assignment
+// inside its expert is its unclipped slot less the expert's unclipped base off[e * nblk]; it stays
+// iff that is below keep[e], at kept_base[e] + position.  Three gathers per placed lane from tables
+// of at most 2048 entries (L2 hits; not staged in LDS, which would cost occupancy).
+template <int DT, bool SCALED, bool CLIP>
 __global__ __launch_bounds__(kBlock) void k_moe_scatter(const void* __restrict__ ids, int is_i64,
                                                         const u32x4* __restrict__ x,
                                                         const float* __restrict__ row_scale, int64_t n, int K,
                                                         int64_t V, int G, int nb, int64_t nblk, int S,
                                                         const int64_t* __restrict__ off,
+                                                        const int64_t* __restrict__ clip,
                                                         u32x4* __restrict__ out_rows, int64_t* __restrict__ slots) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   int32_t* wcnt = reinterpret_cast<int32_t*>(smem);                            // [4][nb]
@@ -107,6 +115,11 @@ __global__ __launch_bounds__(kBlock) void k_moe_scatter(const void* __restrict__
     for (int q = 0; q < w; ++q) inb += wcnt[q * nb + d];
     ps = off[(int64_t)d * nblk + b] + inb;
     MP4X_DASSERT(ps >= 0 && ps < n);
+    if constexpr (CLIP) {
+      const int64_t pe = ps - off[(int64_t)d * nblk];
+      ps = pe < clip[d] ? clip[nb + d] + pe : -1;
+      MP4X_DASSERT(ps < clip[nb - 1] + clip[2 * nb - 1]);          // the kept total
+    }
   }
   if (i < n && part == 0) slots[i] = ps;
   pos[tid] = ps;
@@ -257,12 +270,15 @@ extern "C" int mp4x_moe_route_count(const void* ids, int ids_are_i64, int64_t n,
   return (int)hipGetLastError();
 }
 
-extern "C" int mp4x_moe_route_scatter(int dtype, const void* ids, int ids_are_i64, const void* x,
-                                      const float* row_scale, int64_t n, int K, int64_t row_bytes, int nb,
-                                      void* out_rows, int64_t* slots, void* scratch, size_t scratch_bytes,
-                                      void* stream) {
+namespace {
+// Both scatter entry points: clip == nullptr is the unclipped launch.
+template <bool CLIP>
+int moe_scatter_launch(int dtype, const void* ids, int ids_are_i64, const void* x, const float* row_scale, int64_t n,
+                       int K, int64_t row_bytes, int nb, void* out_rows, int64_t* slots, const int64_t* clip,
+                       void* scratch, size_t scratch_bytes, void* stream) {
   if (int e = moe_dtype_ok(dtype)) return e;
   if (nb < 1 || nb > kMoeMaxNb || n < 0 || K < 1 || n % K || row_bytes < 16 || (row_bytes & 15)) return MP4X_E_BADARG;
+  if (CLIP && (!clip || ((uintptr_t)clip & 7))) return MP4X_E_BADARG;
   if (n == 0) return 0;
   if (n > INT32_MAX / 2 || !ids || ((uintptr_t)ids & (ids_are_i64 ? 7 : 3)) || !x || !out_rows ||
       (((uintptr_t)x | (uintptr_t)out_rows) & 15) || !slots || ((uintptr_t)slots & 7) || ((uintptr_t)row_scale & 3) ||
@@ -276,22 +292,39 @@ extern "C" int mp4x_moe_route_scatter(int dtype, const void* ids, int ids_are_i6
   const int S = tile_split(S_.nblk, V);
   hipStream_t st = (hipStream_t)stream;
   if (!row_scale) {                      // whole rows move as bytes: one instantiation serves every dtype
-    hipLaunchKernelGGL((k_moe_scatter<MP4X_F32, false>), dim3(S_.nblk * S), dim3(kBlock), lds, st, ids, ids_are_i64,
-                       (const u32x4*)x, row_scale, n, K, V, G, nb, S_.nblk, S, (const int64_t*)S_.off, (u32x4*)out_rows,
-                       slots);
+    hipLaunchKernelGGL((k_moe_scatter<MP4X_F32, false, CLIP>), dim3(S_.nblk * S), dim3(kBlock), lds, st, ids,
+                       ids_are_i64, (const u32x4*)x, row_scale, n, K, V, G, nb, S_.nblk, S, (const int64_t*)S_.off, clip,
+                       (u32x4*)out_rows, slots);
     return (int)hipGetLastError();
   }
   return with_dtype(dtype, [&](auto dtc) {
     constexpr int DT = decltype(dtc)::value;
     if constexpr (DT == MP4X_F32 || DT == MP4X_BF16 || DT == MP4X_F16) {
-      hipLaunchKernelGGL((k_moe_scatter<DT, true>), dim3(S_.nblk * S), dim3(kBlock), lds, st, ids, ids_are_i64,
-                         (const u32x4*)x, row_scale, n, K, V, G, nb, S_.nblk, S, (const int64_t*)S_.off,
+      hipLaunchKernelGGL((k_moe_scatter<DT, true, CLIP>), dim3(S_.nblk * S), dim3(kBlock), lds, st, ids, ids_are_i64,
+                         (const u32x4*)x, row_scale, n, K, V, G, nb, S_.nblk, S, (const int64_t*)S_.off, clip,
                          (u32x4*)out_rows, slots);
       return (int)hipGetLastError();
     } else {
       return (int)MP4X_E_UNSUPPORTED;
     }
   });
+}
+}  // namespace
+
+extern "C" int mp4x_moe_route_scatter(int dtype, const void* ids, int ids_are_i64, const void* x,
+                                      const float* row_scale, int64_t n, int K, int64_t row_bytes, int nb,
+                                      void* out_rows, int64_t* slots, void* scratch, size_t scratch_bytes,
+                                      void* stream) {
+  return moe_scatter_launch<false>(dtype, ids, ids_are_i64, x, row_scale, n, K, row_bytes, nb, out_rows, slots, nullptr,
+                                   scratch, scratch_bytes, stream);
+}
+
+extern "C" int mp4x_moe_route_scatter_clip(int dtype, const void* ids, int ids_are_i64, const void* x,
+                                           const float* row_scale, int64_t n, int K, int64_t row_bytes, int nb,
+                                           void* out_rows, int64_t* slots, const int64_t* clip, void* scratch,
+                                           size_t scratch_bytes, void* stream) {
+  return moe_scatter_launch<true>(dtype, ids, ids_are_i64, x, row_scale, n, K, row_bytes, nb, out_rows, slots, clip,
+                                  scratch, scratch_bytes, stream);
 }
 
 extern "C" int mp4x_moe_combine(int dtype, const void* rows, const int64_t* slots, const float* weights, int64_t T,

@@ -15,6 +15,10 @@ does for the same graph on every rank.
 
 :class:`ExpertParallelMoE` is the layer: router linear -> softmax -> top-k -> dispatch -> each
 local expert's two-layer MLP on its ``expert_counts`` slice -> combine with the gate weights.
+
+With an expert capacity (``capacity`` / ``capacity_factor``, see ``dispatchTokens``) the assignments
+past an expert's first C are clipped inside the dispatch: their slots are -1 in the plan, so both
+backward passes leave them out exactly as the forward did.
 """
 from __future__ import annotations
 
@@ -28,15 +32,16 @@ from ..operators import Operators
 
 class _Dispatch(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, comm, expert_ids, num_experts, operand):
-        rows, plan = comm.dispatchTokens(x.contiguous(), expert_ids, num_experts, operand=operand)
+    def forward(ctx, x, comm, expert_ids, num_experts, operand, capacity, capacity_factor):
+        rows, plan = comm.dispatchTokens(x.contiguous(), expert_ids, num_experts, operand=operand, capacity=capacity,
+                                         capacityFactor=capacity_factor)
         ctx.comm, ctx.plan, ctx.operand = comm, plan, operand
         return rows, plan
 
     @staticmethod
     def backward(ctx, g_rows, _plan=None):
         gx = ctx.comm.combineTokens(g_rows.contiguous(), ctx.plan, None, operand=ctx.operand)
-        return gx, None, None, None, None
+        return gx, None, None, None, None, None, None
 
 
 class _Combine(torch.autograd.Function):
@@ -67,9 +72,12 @@ class _Combine(torch.autograd.Function):
         return g_rows, g_w, None, None, None
 
 
-def dispatch_tokens(comm, x: torch.Tensor, expert_ids: torch.Tensor, num_experts: int, operand=None):
-    """Differentiable ``comm.dispatchTokens``: ``(rows, plan)``."""
-    return _Dispatch.apply(x, comm, expert_ids, num_experts, operand)
+def dispatch_tokens(comm, x: torch.Tensor, expert_ids: torch.Tensor, num_experts: int, operand=None, capacity=None,
+                    capacity_factor=None):
+    """Differentiable ``comm.dispatchTokens``: ``(rows, plan)``.  With an expert capacity a clipped
+    assignment has slot -1 in the plan: it takes no part in either backward pass (no gradient
+    reaches its token through it, and its gate weight's gradient is 0)."""
+    return _Dispatch.apply(x, comm, expert_ids, num_experts, operand, capacity, capacity_factor)
 
 
 def combine_tokens(comm, expert_rows: torch.Tensor, plan, weights: Optional[torch.Tensor] = None, operand=None):
@@ -85,10 +93,14 @@ class ExpertParallelMoE(torch.nn.Module):
     the same seed holds exactly the same weights.  After ``backward`` call :meth:`sync_gradients`:
     for a loss that is the mean over ranks of per-rank losses it averages the router's gradient
     over the ranks and scales the experts' (already summed over every rank's tokens by the
-    combine / dispatch backward) by ``1/p``."""
+    combine / dispatch backward) by ``1/p``.
+
+    ``capacity_factor``: every expert accepts the first ``max(1, ceil(f * N / E))`` of the step's N
+    assignments (all ranks') in (rank, token, k) order; the others are dropped (``dispatchTokens``).
+    ``last_plan`` is the last forward's plan (``clipped``, ``demand_matrix``), None before it."""
 
     def __init__(self, comm, d_model: int, d_hidden: int, num_experts: int, top_k: int, seed: int = 0,
-                 device=None, dtype=torch.float32, operand=None):
+                 device=None, dtype=torch.float32, operand=None, capacity_factor=None):
         super().__init__()
         p, r = comm.getSlaveNum(), comm.getRank()
         if num_experts % p:
@@ -96,6 +108,7 @@ class ExpertParallelMoE(torch.nn.Module):
         if not 1 <= top_k <= num_experts:
             raise ValueError("top_k must be in [1, num_experts]")
         self.comm, self.num_experts, self.top_k, self.operand = comm, num_experts, top_k, operand
+        self.capacity_factor, self.last_plan = capacity_factor, None
         self.local_experts = num_experts // p
         self.first_expert = r * self.local_experts
         full = self.init_weights(d_model, d_hidden, num_experts, seed)
@@ -129,7 +142,9 @@ class ExpertParallelMoE(torch.nn.Module):
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         w, ids = self.route(x)
-        rows, plan = dispatch_tokens(self.comm, x, ids, self.num_experts, self.operand)
+        rows, plan = dispatch_tokens(self.comm, x, ids, self.num_experts, self.operand,
+                                     capacity_factor=self.capacity_factor)
+        self.last_plan = plan
         outs, off = [], 0
         for e, c in enumerate(plan.expert_counts):
             h = torch.relu(rows[off:off + c] @ self.w1[e] + self.b1[e])

@@ -479,11 +479,16 @@ def moe_route_count(ids: torch.Tensor, nb: int, stream=None) -> RouteCount:
 
 def moe_route_scatter(rc: RouteCount, x: torch.Tensor, top_k: int, out_rows: torch.Tensor,
                       row_scale: Optional[torch.Tensor] = None, placed: Optional[int] = None,
-                      stream=None) -> torch.Tensor:
+                      stream=None, clip: Optional[torch.Tensor] = None) -> torch.Tensor:
     """K9's scatter after :func:`moe_route_count`: ``slots`` int64[n], the position of assignment
     ``a = t * top_k + k`` in the stable sort by expert id (-1 where it is placed nowhere), and
     ``out_rows[slots[a]] = x[t]``, times ``row_scale[a]`` (float32, one rounding) when given.
-    ``out_rows`` must hold every placed assignment (``rc.counts[:nb].sum()`` rows)."""
+    ``out_rows`` must hold every placed assignment (``rc.counts[:nb].sum()`` rows).
+
+    ``clip`` (int64 ``[2 * nb]`` on the ids' device: ``keep[e]`` | its exclusive prefix): an expert
+    capacity.  The ``pe``-th assignment of expert e stays iff ``pe < keep[e]``, at slot
+    ``prefix[e] + pe``; the others get -1 and their rows are neither read nor written.  ``out_rows``
+    must then hold ``keep.sum()`` rows, which the caller gives as ``placed`` (no sync here)."""
     ids = rc.ids
     n = ids.numel()
     _dev_check(ids, x, out_rows, row_scale)
@@ -494,6 +499,10 @@ def moe_route_scatter(rc: RouteCount, x: torch.Tensor, top_k: int, out_rows: tor
         raise ValueError("moe_route_scatter: out_rows dtype / row shape differ from x")
     if row_scale is not None and (row_scale.dtype != torch.float32 or row_scale.numel() != n):
         raise ValueError("moe_route_scatter: row_scale must be float32, one per assignment")
+    if clip is not None:
+        _dev_check(ids, clip)
+        if clip.dtype != torch.int64 or tuple(clip.shape) != (2 * rc.nb,) or not clip.is_contiguous():
+            raise ValueError(f"moe_route_scatter: clip must be a contiguous int64 [{2 * rc.nb}] tensor")
     slots = torch.empty(n, dtype=torch.int64, device=ids.device)
     if n == 0:
         return slots
@@ -501,17 +510,19 @@ def moe_route_scatter(rc: RouteCount, x: torch.Tensor, top_k: int, out_rows: tor
     # them.  ``placed``: that number when the caller has it on the host already (no sync here).
     if out_rows.shape[0] < n:
         if placed is None:
-            placed = int(rc.counts[:rc.nb].sum())
+            placed = int(rc.counts[:rc.nb].sum()) if clip is None else int(clip[:rc.nb].sum())
         if out_rows.shape[0] < placed:
             raise ValueError("moe_route_scatter: out_rows holds fewer rows than are placed")
     if out_rows.shape[0] == 0:             # nothing is placed: the kernel still wants a valid address
         out_rows = torch.empty((1,) + tuple(x.shape[1:]), dtype=x.dtype, device=x.device)
-    check(native.hip().mp4x_moe_route_scatter(int(dtype_of_torch(x.dtype)), ids.data_ptr(),
-                                              int(ids.dtype == torch.int64), x.data_ptr(),
-                                              row_scale.data_ptr() if row_scale is not None else None, n,
-                                              int(top_k), rb, rc.nb, out_rows.data_ptr(), slots.data_ptr(),
-                                              rc.scratch.data_ptr(), rc.scratch.numel(), stream_ptr(stream)),
-          "mp4x_moe_route_scatter")
+    head = (int(dtype_of_torch(x.dtype)), ids.data_ptr(), int(ids.dtype == torch.int64), x.data_ptr(),
+            row_scale.data_ptr() if row_scale is not None else None, n, int(top_k), rb, rc.nb, out_rows.data_ptr(),
+            slots.data_ptr())
+    tail = (rc.scratch.data_ptr(), rc.scratch.numel(), stream_ptr(stream))
+    if clip is None:
+        check(native.hip().mp4x_moe_route_scatter(*head, *tail), "mp4x_moe_route_scatter")
+    else:
+        check(native.hip().mp4x_moe_route_scatter_clip(*head, clip.data_ptr(), *tail), "mp4x_moe_route_scatter_clip")
     return slots
 
 

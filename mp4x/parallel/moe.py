@@ -20,11 +20,21 @@ Layout contract (``tests/moe_ref.py`` holds it in plain torch):
 One exchange of ``E + 2`` counts per rank (per-expert rows, dropped ids, ids >= E) through
 ``sparse._count_matrix`` serves the dispatch, every later combine and both backward passes.
 
+Expert capacity (``capacity`` / ``capacity_factor``): expert e accepts the first C assignments in
+the global order (source rank, then the sender's flattened assignment index).  After the count
+exchange every rank holds the whole demand matrix ``D[i][e]``, so the rows of expert e that rank i
+may keep, ``keep[i][e] = min(D[i][e], max(0, C - sum_{j<i} D[j][e]))`` (:func:`capacity_quota`),
+cost no further exchange; the scatter half of the route compares an assignment's position inside
+its expert with that quota and gives a clipped assignment slot -1.  A capped call is, bit for bit,
+the uncapped call on the ids with every clipped assignment replaced by -1: clipped rows are never
+read, written or sent, every later combine skips them, and both backward passes follow the plan.
+
 GPU tensors run the K9 kernels (``csrc/kernels/moe.hip``); host tensors, and GPU tensors where
 the native library is absent, run the torch implementation of the same contract below.
 """
 from __future__ import annotations
 
+import math
 from typing import List, Optional, Sequence, Tuple
 
 import torch
@@ -43,11 +53,19 @@ class TokenPlan:
     of every local expert (the groups of the dispatched rows, ascending).  ``send_counts`` /
     ``recv_counts``: rows to / from every rank.  ``slots``: int64 ``[T*K]`` on the tokens' device.
     ``matrix[i][j]``: rows rank i sends to rank j.  ``expert_matrix[i][e]``: rows rank i sends to
-    global expert e."""
+    global expert e.
+
+    With an expert capacity all of the above describe the rows that stayed.  ``capacity``: the
+    resolved C of the call (None: no capacity).  ``demand_matrix[i][e]``: the assignments of rank i
+    with expert e before clipping (``expert_matrix`` itself when there is no capacity): what a
+    load-balancing loss or a monitor wants.  ``clipped``: this rank's assignments the capacity
+    dropped, ``sum_e demand_matrix[r][e] - expert_matrix[r][e]``."""
     __slots__ = ("num_tokens", "top_k", "num_experts", "expert_counts", "send_counts", "recv_counts", "slots",
-                 "matrix", "expert_matrix", "row_shape", "dtype", "rank", "_route", "_frozen")
+                 "matrix", "expert_matrix", "row_shape", "dtype", "rank", "capacity", "demand_matrix", "clipped",
+                 "_route", "_clip", "_frozen")
 
     def __init__(self, **kw):
+        kw = {"capacity": None, "demand_matrix": kw.get("expert_matrix"), "clipped": 0, "_clip": None, **kw}
         for k, v in kw.items():
             object.__setattr__(self, k, v)
         object.__setattr__(self, "_frozen", True)
@@ -128,6 +146,53 @@ def _torch_combine(rows: torch.Tensor, slots: torch.Tensor, weights: Optional[to
     return acc.to(rows.dtype)
 
 
+def _torch_clip(route, ids: torch.Tensor, nb: int, keep: Sequence[int]):
+    """``_torch_route``'s result under the quota ``keep[e]``: the assignments past it leave the
+    slots and the order; the others close ranks (still the stable sort)."""
+    counts, slots, order = route
+    keep_t = torch.tensor(list(keep), dtype=torch.int64, device=ids.device)
+    start = torch.cumsum(counts[:nb], 0) - counts[:nb]
+    e = ids.to(torch.int64)[order]
+    pe = torch.arange(order.numel(), dtype=torch.int64, device=ids.device) - start[e]
+    order = order[pe < keep_t[e]]
+    slots = torch.full_like(slots, -1)
+    slots[order] = torch.arange(order.numel(), dtype=torch.int64, device=ids.device)
+    return counts, slots, order
+
+
+# ---------------------------------------------------------------- expert capacity
+def capacity_quota(demand: Sequence[Sequence[int]], capacity: int) -> Tuple[Tuple[int, ...], ...]:
+    """``keep[i][e] = min(D[i][e], max(0, C - sum_{j<i} D[j][e]))``: the rows of expert e that rank
+    i keeps when every expert accepts the first ``capacity`` assignments in (rank, assignment)
+    order.  A pure function of the demand matrix ``D[i][e]``, the same on every rank."""
+    C = int(capacity)
+    keep, used = [], [0] * (len(demand[0]) if len(demand) else 0)
+    for row in demand:
+        keep.append(tuple(min(int(d), max(0, C - u)) for d, u in zip(row, used)))
+        used = [u + int(d) for d, u in zip(row, used)]
+    return tuple(keep)
+
+
+def _check_capacity(capacity, capacity_factor):
+    """The caller's contract, the same on every rank: refused before the count exchange."""
+    if capacity is not None and capacity_factor is not None:
+        raise Mp4jException("dispatchTokens: give capacity or capacityFactor, not both")
+    if capacity is not None and (isinstance(capacity, bool) or not isinstance(capacity, int) or capacity < 1):
+        raise Mp4jException(f"dispatchTokens: capacity {capacity!r} is not an int >= 1")
+    if capacity_factor is not None:
+        f = capacity_factor
+        if isinstance(f, bool) or not isinstance(f, (int, float)) or not math.isfinite(f) or f <= 0:
+            raise Mp4jException(f"dispatchTokens: capacityFactor {f!r} is not a finite float > 0")
+
+
+def _resolve_capacity(capacity, capacity_factor, assignments: int, E: int) -> Optional[int]:
+    """C of the call: ``capacity`` itself, or ``max(1, ceil(f * N / E))`` with N the assignments
+    of all ranks (negative ids included), which the count exchange gave every rank."""
+    if capacity_factor is not None:
+        return max(1, math.ceil(float(capacity_factor) * assignments / E))
+    return capacity
+
+
 # ---------------------------------------------------------------- count matrix, regroup
 def _segments(plan: TokenPlan) -> List[Tuple[int, int, int]]:
     """(expert-major row offset, source-major row offset, rows) of every (source, local expert)
@@ -183,22 +248,26 @@ def _exchange(engine, send: torch.Tensor, send_counts, mat, operand):
 
 
 # ---------------------------------------------------------------- dispatch
-def _route_rows(x: torch.Tensor, plan_route, top_k: int, placed: int, row_scale: Optional[torch.Tensor]):
-    """Rows of ``x`` replicated into send order (the second half of the route)."""
+def _route_rows(x: torch.Tensor, plan_route, top_k: int, placed: int, row_scale: Optional[torch.Tensor],
+                clip: Optional[torch.Tensor] = None):
+    """Rows of ``x`` replicated into send order (the second half of the route).  ``clip``: the
+    device ``[keep | kept_base]`` of a capped call (the torch form's route is clipped already)."""
     if _native_ok(x):
         from ..ops.device_ops import moe_route_scatter
         out = torch.empty((placed,) + tuple(x.shape[1:]), dtype=x.dtype, device=x.device)
-        slots = moe_route_scatter(plan_route, x, top_k, out, row_scale=row_scale, placed=placed)
+        slots = moe_route_scatter(plan_route, x, top_k, out, row_scale=row_scale, placed=placed, clip=clip)
         return out, slots
     _, slots, order = plan_route
     return _torch_scatter(x, order, top_k, row_scale), slots
 
 
-def dispatch(engine, x: torch.Tensor, expert_ids: torch.Tensor, num_experts: int, operand=None):
+def dispatch(engine, x: torch.Tensor, expert_ids: torch.Tensor, num_experts: int, operand=None, capacity=None,
+             capacity_factor=None):
     """``(rows, plan)``: see ``ProcessCommSlave.dispatchTokens``."""
     p, r = engine.p, engine.rank
     E = int(num_experts)
     _check_rows("dispatchTokens", x)
+    _check_capacity(capacity, capacity_factor)
     if E < 1 or E % p:
         raise Mp4jException(f"dispatchTokens: numExperts {E} is not a positive multiple of the {p} ranks")
     if E > MAX_EXPERTS:
@@ -232,16 +301,31 @@ def dispatch(engine, x: torch.Tensor, expert_ids: torch.Tensor, num_experts: int
     bad = [(j, int(row[E + 1])) for j, row in enumerate(rows_) if row[E + 1]]
     if bad:
         raise Mp4jException(f"dispatchTokens: rank {bad[0][0]} has {bad[0][1]} expert id(s) >= numExperts {E}")
+    # an expert capacity: every rank works out every rank's quota from the demand matrix
+    demand, clip, clipped = emat, None, 0
+    C = _resolve_capacity(capacity, capacity_factor, sum(int(v) for row in rows_ for v in row[:E + 1]), E)
+    if C is not None:
+        emat = capacity_quota(demand, C)
+        keep = emat[r]
+        clipped = sum(demand[r]) - sum(keep)
+        if native:
+            kbase = [0] * E
+            for e in range(1, E):
+                kbase[e] = kbase[e - 1] + keep[e - 1]
+            clip = torch.tensor(list(keep) + kbase, dtype=torch.int64).to(x.device)      # one small H2D copy
+        else:
+            route = _torch_clip(route, ids, E, keep)
     el = E // p
     mat = tuple(tuple(sum(emat[i][j * el:(j + 1) * el]) for j in range(p)) for i in range(p))
     send_counts = mat[r]
     recv_counts = tuple(mat[i][r] for i in range(p))
     expert_counts = tuple(sum(emat[i][r * el + e] for i in range(p)) for e in range(el))
     # 3. route scatter
-    send, slots = _route_rows(x, route, K, sum(send_counts), None)
+    send, slots = _route_rows(x, route, K, sum(send_counts), None, clip)
     plan = TokenPlan(num_tokens=T, top_k=K, num_experts=E, expert_counts=expert_counts, send_counts=send_counts,
                      recv_counts=recv_counts, slots=slots, matrix=mat, expert_matrix=emat,
-                     row_shape=tuple(x.shape[1:]), dtype=x.dtype, rank=r, _route=route)
+                     row_shape=tuple(x.shape[1:]), dtype=x.dtype, rank=r, capacity=C, demand_matrix=demand,
+                     clipped=clipped, _route=route, _clip=clip)
     # 4. the all-to-all with that matrix, 5. expert-major
     return _forward_rows(engine, send, plan, operand), plan
 
@@ -256,11 +340,11 @@ def _forward_rows(engine, send: torch.Tensor, plan: TokenPlan, operand):
 def dispatch_scaled(engine, x: torch.Tensor, plan: TokenPlan, row_scale: Optional[torch.Tensor], operand=None):
     """Dispatch ``x`` [T, ...] again along ``plan`` with every assignment's row times
     ``row_scale`` [T, K] (the combine's backward w.r.t. the expert rows): the route scatter with
-    the plan's scan and matrix, no count exchange."""
+    the plan's scan, clipping and matrix, no count exchange."""
     _check_rows("dispatchTokens", x)
     _check_plan_rows("dispatchTokens", x, plan, plan.num_tokens)
     row_scale = _check_weights(row_scale, plan, x)
-    send, _ = _route_rows(x, plan._route, plan.top_k, sum(plan.send_counts), row_scale)
+    send, _ = _route_rows(x, plan._route, plan.top_k, sum(plan.send_counts), row_scale, plan._clip)
     return _forward_rows(engine, send, plan, operand)
 
 

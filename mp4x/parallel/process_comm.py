@@ -946,7 +946,8 @@ class ProcessCommSlave:
             raise Mp4jException("alltoallArray needs a torch tensor (device engine)")
         return self.device.all_to_all_v(sendData, list(sendCounts), recvData, operand)
 
-    def dispatchTokens(self, x, expertIds, numExperts: int, operand: Optional[Operand] = None):
+    def dispatchTokens(self, x, expertIds, numExperts: int, operand: Optional[Operand] = None, capacity=None,
+                       capacityFactor=None):
         """Expert-parallel token dispatch (extension, over ``alltoallArray``'s transport).
 
         ``x`` is ``[T, ...]`` (contiguous; f32 / bf16 / f16), ``expertIds`` ``[T, K]`` or ``[T]``
@@ -965,14 +966,34 @@ class ProcessCommSlave:
         unchanged (``codec="fp8"``: see :meth:`alltoallArray`).  Host tensors take a torch
         implementation of the same contract.
 
+        Expert capacity: ``capacity`` (an int ``C >= 1``, one value for every expert) or
+        ``capacityFactor`` (a float ``f > 0``: ``C = max(1, ceil(f * N / E))`` with N the
+        assignments of all ranks, negative ids included), the same on every rank like
+        ``numExperts``.  Expert e accepts the first C assignments in the global order (source
+        rank, then the sender's flattened assignment index ``t*K + k``): what one process holding
+        every rank's tokens concatenated rank-major would keep first-come.  With ``D[i][e]`` the
+        assignments of rank i with expert e (known everywhere after the count exchange), rank i
+        keeps ``keep[i][e] = min(D[i][e], max(0, C - sum_{j<i} D[j][e]))`` of them
+        (``mp4x.parallel.moe.capacity_quota``), its first in assignment order; the others are
+        clipped in the route scatter: ``plan.slots`` is -1 there, their rows are never read,
+        written or sent, and the call equals, bit for bit, the uncapped call on the ids with
+        every clipped assignment set to -1 (rows, slots, counts and matrices; every later
+        :meth:`combineTokens`, where a wholly clipped token gets zeros).  No further exchange:
+        still ``E + 2`` counts once.  ``plan.capacity`` is the resolved C (None without one),
+        ``plan.demand_matrix`` the unclipped ``D`` (``plan.expert_matrix`` holds what stayed) and
+        ``plan.clipped`` this rank's clipped assignments.
+
         Raises :class:`Mp4jException`, on every rank alike and before any row moves, for ``E``
         not a multiple of the rank count or above 2048, mismatched shapes, an id ``>= E`` on any
         rank (the message names the rank), another dtype, GPU rows that are not whole 16-byte
-        vectors, and a call inside a graph capture (the count exchange is a host sync)."""
+        vectors, both ``capacity`` and ``capacityFactor``, a ``capacity`` that is not an int
+        ``>= 1`` (a bool is refused), a ``capacityFactor`` that is not a finite number ``> 0``,
+        and a call inside a graph capture (the count exchange is a host sync)."""
         self._tick("dispatchTokens")
         if not _is_torch(x):
             raise Mp4jException("dispatchTokens needs a torch tensor (device engine)")
-        return self.device.dispatch_tokens(x, expertIds, numExperts, operand)
+        return self.device.dispatch_tokens(x, expertIds, numExperts, operand, capacity=capacity,
+                                           capacity_factor=capacityFactor)
 
     def combineTokens(self, expertRows, plan, weights=None, operand: Optional[Operand] = None,
                       returnSlotRows: bool = False):
