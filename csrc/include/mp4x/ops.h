@@ -197,6 +197,25 @@ int mp4x_moe_route_scatter_clip(int dtype, const void* ids, int ids_are_i64, con
 // FMA), w = weights ? weights[t*K+k] : 1.  Rows of `width` elements, whole 16-byte vectors.
 int mp4x_moe_combine(int dtype, const void* rows, const int64_t* slots, const float* weights, int64_t T, int K,
                      int64_t width, void* out, void* stream);
+// The padded fixed-capacity layout (a per-source share): out_rows holds nb * cap rows, expert e owns
+// the block [e * cap, (e + 1) * cap).  slots[a] = pe < cap ? e * cap + pe : -1 with pe as above; a
+// negative id and an id >= nb get -1.  Every row of out_rows is written exactly once per call: row
+// e * cap + pe by the scatter, the rows [min(cnt[e], cap), cap) of every block as all-zero bits by
+// a fill kernel after it (no memset of the buffer).  n == 0 writes nb * cap zero rows and needs
+// neither ids, x, slots nor scratch.  1 <= cap <= INT32_MAX / nb, else MP4X_E_BADARG.
+int mp4x_moe_route_scatter_pad(int dtype, const void* ids, int ids_are_i64, const void* x, const float* row_scale,
+                               int64_t n, int K, int64_t row_bytes, int nb, int64_t cap, void* out_rows, int64_t* slots,
+                               void* scratch, size_t scratch_bytes, void* stream);
+// After mp4x_moe_route_count on the same scratch (none when n == 0): kept[(e / el) * el_pad + e % el]
+// = min(cnt[e], cap) for the nb experts in groups of el (nb % el == 0; el_pad >= el, the padding is
+// zeroed; el_pad == el is the plain int64[nb]) and dropped[3] = assignments past their share |
+// negative ids | ids >= nb.
+int mp4x_moe_pad_counts(int64_t n, int nb, int64_t cap, int el, int el_pad, int64_t* kept, int64_t* dropped,
+                        void* scratch, size_t scratch_bytes, void* stream);
+// mp4x_moe_combine over a buffer of num_rows >= 1 rows that the slots index anywhere (the padded
+// layout: slots reach nb * cap - 1, which may exceed T * K).  Rows no slot names are never read.
+int mp4x_moe_combine_rows(int dtype, const void* rows, int64_t num_rows, const int64_t* slots, const float* weights,
+                          int64_t T, int K, int64_t width, void* out, void* stream);
 
 // ---------------------------------------------------------------- errors
 // Reads and clears this thread's last HIP error.  mp4x reports its own failures through return

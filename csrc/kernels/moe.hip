@@ -15,7 +15,12 @@
 //                  optionally scaled per assignment (one multiply per element, one rounding);
 //                  up to 16 blocks share a tile of long rows (tile_split); with an expert
 //                  capacity (CLIP) an assignment past its expert's quota gets slot -1 there and
-//                  its row is neither read nor written
+//                  its row is neither read nor written; with a per-source share (PAD) the
+//                  pe-th assignment of expert e goes to the fixed slot e * cap + pe iff pe < cap
+//   pad fill       k_moe_pad_fill  zeros to the rows [min(cnt[e], cap), cap) of every expert block
+//                  of the padded layout, so every row of the buffer is written exactly once
+//   pad counts     k_moe_pad_counts  kept[e] = min(cnt[e], cap) and dropped[3] (over the share,
+//                  negative, >= nb) from the scanned bases
 //   combine        k_moe_combine  out[t] = sum over k, in k order, of w[t, k] * rows[slots[t, k]]:
 //                  a lane group per token reads its K rows through the slot index; the mul and
 //                  the add are separate roundings (no contraction), one rounding to the dtype
@@ -77,13 +82,20 @@ __global__ __launch_bounds__(kBlock) void k_moe_counts(const int64_t* __restrict
 // inside its expert is its unclipped slot less the expert's unclipped base off[e * nblk]; it stays
 // iff that is below keep[e], at kept_base[e] + position.  Three gathers per placed lane from tables
 // of at most 2048 entries (L2 hits; not staged in LDS, which would cost occupancy).
-template <int DT, bool SCALED, bool CLIP>
+//
+// PAD (a per-source share, the padded fixed-capacity layout): every expert owns the block of `cap`
+// rows [e * cap, (e + 1) * cap) whatever the ids are; the position stays iff it is below cap, at
+// e * cap + position.  cap is a scalar: no table at all.  The rows of a block no assignment reaches
+// are k_moe_pad_fill's.
+enum : int { kMoePlain = 0, kMoeClip = 1, kMoePad = 2 };
+
+template <int DT, bool SCALED, int MODE>
 __global__ __launch_bounds__(kBlock) void k_moe_scatter(const void* __restrict__ ids, int is_i64,
                                                         const u32x4* __restrict__ x,
                                                         const float* __restrict__ row_scale, int64_t n, int K,
                                                         int64_t V, int G, int nb, int64_t nblk, int S,
                                                         const int64_t* __restrict__ off,
-                                                        const int64_t* __restrict__ clip,
+                                                        const int64_t* __restrict__ clip, int64_t cap,
                                                         u32x4* __restrict__ out_rows, int64_t* __restrict__ slots) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   int32_t* wcnt = reinterpret_cast<int32_t*>(smem);                            // [4][nb]
@@ -115,10 +127,15 @@ __global__ __launch_bounds__(kBlock) void k_moe_scatter(const void* __restrict__
     for (int q = 0; q < w; ++q) inb += wcnt[q * nb + d];
     ps = off[(int64_t)d * nblk + b] + inb;
     MP4X_DASSERT(ps >= 0 && ps < n);
-    if constexpr (CLIP) {
+    if constexpr (MODE == kMoeClip) {
       const int64_t pe = ps - off[(int64_t)d * nblk];
       ps = pe < clip[d] ? clip[nb + d] + pe : -1;
       MP4X_DASSERT(ps < clip[nb - 1] + clip[2 * nb - 1]);          // the kept total
+    }
+    if constexpr (MODE == kMoePad) {
+      const int64_t pe = ps - off[(int64_t)d * nblk];
+      ps = pe < cap ? (int64_t)d * cap + pe : -1;
+      MP4X_DASSERT(ps < (int64_t)nb * cap);
     }
   }
   if (i < n && part == 0) slots[i] = ps;
@@ -160,13 +177,66 @@ __global__ __launch_bounds__(kBlock) void k_moe_scatter(const void* __restrict__
   }
 }
 
+// The pad rows of the padded layout.  The rows [min(cnt[e], cap), cap) of expert e's block are one
+// contiguous span of (cap - kept) * V vectors, so the lanes of a block walk it vector by vector
+// (consecutive lanes, consecutive 16-byte nontemporal stores: whole 1 KiB lines per wave, which a
+// lane group per row would only reach for V >= 64); blockIdx.y is the expert, blockIdx.x strides
+// over the span.  cnt[e] comes from the scanned bases; off == nullptr is the call with no
+// assignment at all (nothing was scanned): every row is pad.
+__global__ __launch_bounds__(kBlock) void k_moe_pad_fill(const int64_t* __restrict__ off, int64_t nblk, int64_t cap,
+                                                         int64_t V, u32x4* __restrict__ out_rows) {
+  const int e = blockIdx.y;
+  int64_t kept = 0;
+  if (off) {
+    kept = off[(int64_t)(e + 1) * nblk] - off[(int64_t)e * nblk];       // bucket e + 1 exists: nb + 2 buckets
+    if (kept > cap) kept = cap;
+  }
+  const int64_t span = (cap - kept) * V;
+  u32x4* dst = out_rows + ((int64_t)e * cap + kept) * V;
+  const u32x4 zero = {0u, 0u, 0u, 0u};
+  for (int64_t v = (int64_t)blockIdx.x * kBlock + threadIdx.x; v < span; v += (int64_t)gridDim.x * kBlock)
+    __builtin_nontemporal_store(zero, dst + v);
+}
+
+// One block: kept[e] = min(cnt[e], cap), written at wire[(e / el) * el_pad + e % el] (el_pad >= el:
+// every destination rank's counts start on a 16-byte boundary of the exchange; el_pad == el is the
+// plain [nb] vector), and dropped = {over the share, negative ids, ids >= nb}.  Integer sums only:
+// identical run to run.  off == nullptr: no assignment at all.
+__global__ __launch_bounds__(kBlock) void k_moe_pad_counts(const int64_t* __restrict__ off,
+                                                           const int64_t* __restrict__ hist, int nb, int64_t nblk,
+                                                           int64_t cap, int el, int el_pad, int64_t* __restrict__ wire,
+                                                           int64_t* __restrict__ dropped) {
+  __shared__ unsigned long long over;
+  if (threadIdx.x == 0) over = 0;
+  __syncthreads();
+  unsigned long long mine = 0;
+  for (int e = threadIdx.x; e < nb; e += kBlock) {
+    const int64_t c = off ? off[(int64_t)(e + 1) * nblk] - off[(int64_t)e * nblk] : 0;
+    const int64_t k = c < cap ? c : cap;
+    wire[(int64_t)(e / el) * el_pad + e % el] = k;
+    mine += (unsigned long long)(c - k);
+  }
+  for (int q = threadIdx.x; q < (nb / el) * (el_pad - el); q += kBlock)      // the wire's padding
+    wire[(int64_t)(q / (el_pad - el)) * el_pad + el + q % (el_pad - el)] = 0;
+  if (mine) atomicAdd(&over, mine);
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const int64_t last = (int64_t)(nb + 2) * nblk - 1;
+    dropped[0] = (int64_t)over;
+    dropped[1] = off ? off[(int64_t)(nb + 1) * nblk] - off[(int64_t)nb * nblk] : 0;
+    dropped[2] = off ? off[last] + hist[last] - off[(int64_t)(nb + 1) * nblk] : 0;
+  }
+}
+
 // G lanes per token (64 / G tokens per wave); a lane owns the 16-byte vectors sub, sub + G, ... of
-// the row and walks the token's K slots in k order.
+// the row and walks the token's K slots in k order.  nrows bounds a slot (debug builds): T * K in
+// the ragged layout, nb * cap in the padded one.
 template <int DT>
 __global__ __launch_bounds__(kBlock) void k_moe_combine(const u32x4* __restrict__ rows,
                                                         const int64_t* __restrict__ slots,
                                                         const float* __restrict__ weights, int64_t T, int K,
-                                                        int64_t V, int G, u32x4* __restrict__ out) {
+                                                        int64_t V, int G, int64_t nrows,
+                                                        u32x4* __restrict__ out) {
   constexpr int W = 16 / sizeof(typename Elem<DT>::S);
   const int lane = threadIdx.x & 63;
   const int grp = lane / G, sub = lane % G, R = 64 / G;
@@ -182,7 +252,7 @@ __global__ __launch_bounds__(kBlock) void k_moe_combine(const u32x4* __restrict_
       for (int k = 0; k < K; ++k) {
         const int64_t s = sl[k];
         if (s < 0) continue;
-        MP4X_DASSERT(s < T * K);
+        MP4X_DASSERT(s < nrows);
         const float wk = wt ? wt[k] : 1.0f;
         float a[W];
         unpack<DT>(rows[s * V + v], a);
@@ -271,15 +341,30 @@ extern "C" int mp4x_moe_route_count(const void* ids, int ids_are_i64, int64_t n,
 }
 
 namespace {
-// Both scatter entry points: clip == nullptr is the unclipped launch.
-template <bool CLIP>
+// The pad rows of every expert block; sc == nullptr: no assignment, the whole buffer is pad.
+int moe_pad_fill_launch(const MoeScratch* sc, int nb, int64_t cap, int64_t V, void* out_rows, hipStream_t st) {
+  const int64_t span = cap * V;
+  int64_t gx = (span + 4 * kBlock - 1) / (4 * kBlock);           // >= 4 vectors (64 B) per lane of a full block
+  const int64_t room = 4096 / nb;                                // ... and about 16 blocks per CU in all
+  if (gx > room) gx = room;
+  if (gx < 1) gx = 1;
+  hipLaunchKernelGGL(k_moe_pad_fill, dim3((unsigned)gx, (unsigned)nb), dim3(kBlock), 0, st,
+                     sc ? (const int64_t*)sc->off : (const int64_t*)nullptr, sc ? sc->nblk : 0, cap, V, (u32x4*)out_rows);
+  return (int)hipGetLastError();
+}
+
+// The scatter entry points: kMoePlain has no table, kMoeClip reads clip, kMoePad the scalar cap.
+template <int MODE>
 int moe_scatter_launch(int dtype, const void* ids, int ids_are_i64, const void* x, const float* row_scale, int64_t n,
                        int K, int64_t row_bytes, int nb, void* out_rows, int64_t* slots, const int64_t* clip,
-                       void* scratch, size_t scratch_bytes, void* stream) {
+                       int64_t cap, void* scratch, size_t scratch_bytes, void* stream) {
+  constexpr bool PAD = MODE == kMoePad;
   if (int e = moe_dtype_ok(dtype)) return e;
   if (nb < 1 || nb > kMoeMaxNb || n < 0 || K < 1 || n % K || row_bytes < 16 || (row_bytes & 15)) return MP4X_E_BADARG;
-  if (CLIP && (!clip || ((uintptr_t)clip & 7))) return MP4X_E_BADARG;
-  if (n == 0) return 0;
+  if (MODE == kMoeClip && (!clip || ((uintptr_t)clip & 7))) return MP4X_E_BADARG;
+  // the padded buffer is written whole even without an assignment: it is checked before the empty call
+  if (PAD && (cap < 1 || cap > INT32_MAX / nb || !out_rows || ((uintptr_t)out_rows & 15))) return MP4X_E_BADARG;
+  if (n == 0) return PAD ? moe_pad_fill_launch(nullptr, nb, cap, row_bytes / 16, out_rows, (hipStream_t)stream) : 0;
   if (n > INT32_MAX / 2 || !ids || ((uintptr_t)ids & (ids_are_i64 ? 7 : 3)) || !x || !out_rows ||
       (((uintptr_t)x | (uintptr_t)out_rows) & 15) || !slots || ((uintptr_t)slots & 7) || ((uintptr_t)row_scale & 3) ||
       !scratch || ((uintptr_t)scratch & 255))
@@ -292,22 +377,25 @@ int moe_scatter_launch(int dtype, const void* ids, int ids_are_i64, const void* 
   const int S = tile_split(S_.nblk, V);
   hipStream_t st = (hipStream_t)stream;
   if (!row_scale) {                      // whole rows move as bytes: one instantiation serves every dtype
-    hipLaunchKernelGGL((k_moe_scatter<MP4X_F32, false, CLIP>), dim3(S_.nblk * S), dim3(kBlock), lds, st, ids,
-                       ids_are_i64, (const u32x4*)x, row_scale, n, K, V, G, nb, S_.nblk, S, (const int64_t*)S_.off, clip,
+    hipLaunchKernelGGL((k_moe_scatter<MP4X_F32, false, MODE>), dim3(S_.nblk * S), dim3(kBlock), lds, st, ids,
+                       ids_are_i64, (const u32x4*)x, row_scale, n, K, V, G, nb, S_.nblk, S, (const int64_t*)S_.off, clip, cap,
                        (u32x4*)out_rows, slots);
-    return (int)hipGetLastError();
+    if (int e = (int)hipGetLastError()) return e;
+    return PAD ? moe_pad_fill_launch(&S_, nb, cap, V, out_rows, st) : 0;
   }
-  return with_dtype(dtype, [&](auto dtc) {
+  const int e = with_dtype(dtype, [&](auto dtc) {
     constexpr int DT = decltype(dtc)::value;
     if constexpr (DT == MP4X_F32 || DT == MP4X_BF16 || DT == MP4X_F16) {
-      hipLaunchKernelGGL((k_moe_scatter<DT, true, CLIP>), dim3(S_.nblk * S), dim3(kBlock), lds, st, ids, ids_are_i64,
-                         (const u32x4*)x, row_scale, n, K, V, G, nb, S_.nblk, S, (const int64_t*)S_.off, clip,
+      hipLaunchKernelGGL((k_moe_scatter<DT, true, MODE>), dim3(S_.nblk * S), dim3(kBlock), lds, st, ids, ids_are_i64,
+                         (const u32x4*)x, row_scale, n, K, V, G, nb, S_.nblk, S, (const int64_t*)S_.off, clip, cap,
                          (u32x4*)out_rows, slots);
       return (int)hipGetLastError();
     } else {
       return (int)MP4X_E_UNSUPPORTED;
     }
   });
+  if (e) return e;
+  return PAD ? moe_pad_fill_launch(&S_, nb, cap, V, out_rows, st) : 0;
 }
 }  // namespace
 
@@ -315,20 +403,54 @@ extern "C" int mp4x_moe_route_scatter(int dtype, const void* ids, int ids_are_i6
                                       const float* row_scale, int64_t n, int K, int64_t row_bytes, int nb,
                                       void* out_rows, int64_t* slots, void* scratch, size_t scratch_bytes,
                                       void* stream) {
-  return moe_scatter_launch<false>(dtype, ids, ids_are_i64, x, row_scale, n, K, row_bytes, nb, out_rows, slots, nullptr,
-                                   scratch, scratch_bytes, stream);
+  return moe_scatter_launch<kMoePlain>(dtype, ids, ids_are_i64, x, row_scale, n, K, row_bytes, nb, out_rows, slots,
+                                       nullptr, 0, scratch, scratch_bytes, stream);
 }
 
 extern "C" int mp4x_moe_route_scatter_clip(int dtype, const void* ids, int ids_are_i64, const void* x,
                                            const float* row_scale, int64_t n, int K, int64_t row_bytes, int nb,
                                            void* out_rows, int64_t* slots, const int64_t* clip, void* scratch,
                                            size_t scratch_bytes, void* stream) {
-  return moe_scatter_launch<true>(dtype, ids, ids_are_i64, x, row_scale, n, K, row_bytes, nb, out_rows, slots, clip,
-                                  scratch, scratch_bytes, stream);
+  return moe_scatter_launch<kMoeClip>(dtype, ids, ids_are_i64, x, row_scale, n, K, row_bytes, nb, out_rows, slots, clip,
+                                      0, scratch, scratch_bytes, stream);
 }
 
-extern "C" int mp4x_moe_combine(int dtype, const void* rows, const int64_t* slots, const float* weights, int64_t T,
-                                int K, int64_t width, void* out, void* stream) {
+// The padded fixed-capacity layout: out_rows holds nb * cap rows and every one of them is written
+// exactly once, the kept rows by the scatter and the pad rows [min(cnt[e], cap), cap) of every
+// expert block by the fill (a kernel of its own: it also serves the call with no assignment, where
+// the scatter has no tile to launch, and its grid follows the expert blocks, not the tiles).
+extern "C" int mp4x_moe_route_scatter_pad(int dtype, const void* ids, int ids_are_i64, const void* x,
+                                          const float* row_scale, int64_t n, int K, int64_t row_bytes, int nb,
+                                          int64_t cap, void* out_rows, int64_t* slots, void* scratch,
+                                          size_t scratch_bytes, void* stream) {
+  return moe_scatter_launch<kMoePad>(dtype, ids, ids_are_i64, x, row_scale, n, K, row_bytes, nb, out_rows, slots,
+                                     nullptr, cap, scratch, scratch_bytes, stream);
+}
+
+// kept (min(cnt[e], cap), laid out [nb / el][el_pad]) and dropped[3] after mp4x_moe_route_count on
+// the same scratch; n == 0 needs no scratch.
+extern "C" int mp4x_moe_pad_counts(int64_t n, int nb, int64_t cap, int el, int el_pad, int64_t* kept, int64_t* dropped,
+                                   void* scratch, size_t scratch_bytes, void* stream) {
+  if (nb < 1 || nb > kMoeMaxNb || n < 0 || n > INT32_MAX / 2 || cap < 1 || el < 1 || nb % el || el_pad < el || !kept ||
+      ((uintptr_t)kept & 7) || !dropped || ((uintptr_t)dropped & 7))
+    return MP4X_E_BADARG;
+  hipStream_t st = (hipStream_t)stream;
+  if (n == 0) {
+    hipLaunchKernelGGL(k_moe_pad_counts, dim3(1), dim3(kBlock), 0, st, (const int64_t*)nullptr, (const int64_t*)nullptr,
+                       nb, (int64_t)0, cap, el, el_pad, kept, dropped);
+    return (int)hipGetLastError();
+  }
+  if (!scratch || ((uintptr_t)scratch & 255) || scratch_bytes < mp4x_moe_route_scratch_bytes(n, nb)) return MP4X_E_BADARG;
+  const MoeScratch S = moe_scratch(scratch, scratch_bytes, n, nb);
+  hipLaunchKernelGGL(k_moe_pad_counts, dim3(1), dim3(kBlock), 0, st, (const int64_t*)S.off, (const int64_t*)S.hist, nb,
+                     S.nblk, cap, el, el_pad, kept, dropped);
+  return (int)hipGetLastError();
+}
+
+namespace {
+// Both combine entry points: num_rows < 0 is the ragged layout's bound T * K.
+int moe_combine_launch(int dtype, const void* rows, int64_t num_rows, const int64_t* slots, const float* weights,
+                       int64_t T, int K, int64_t width, void* out, void* stream) {
   if (int e = moe_dtype_ok(dtype)) return e;
   const int64_t row_bytes = width * elem_size(dtype);
   if (T < 0 || K < 1 || width < 1 || (row_bytes & 15)) return MP4X_E_BADARG;
@@ -346,10 +468,23 @@ extern "C" int mp4x_moe_combine(int dtype, const void* rows, const int64_t* slot
     constexpr int DT = decltype(dtc)::value;
     if constexpr (DT == MP4X_F32 || DT == MP4X_BF16 || DT == MP4X_F16) {
       hipLaunchKernelGGL((k_moe_combine<DT>), dim3(g), dim3(kBlock), 0, st, (const u32x4*)rows, slots, weights, T, K, V,
-                         G, (u32x4*)out);
+                         G, num_rows < 0 ? T * K : num_rows, (u32x4*)out);
       return (int)hipGetLastError();
     } else {
       return (int)MP4X_E_UNSUPPORTED;
     }
   });
+}
+}  // namespace
+
+extern "C" int mp4x_moe_combine(int dtype, const void* rows, const int64_t* slots, const float* weights, int64_t T,
+                                int K, int64_t width, void* out, void* stream) {
+  return moe_combine_launch(dtype, rows, -1, slots, weights, T, K, width, out, stream);
+}
+
+// The combine of the padded layout: slots reach num_rows - 1 = nb * cap - 1, which may exceed T * K.
+extern "C" int mp4x_moe_combine_rows(int dtype, const void* rows, int64_t num_rows, const int64_t* slots,
+                                     const float* weights, int64_t T, int K, int64_t width, void* out, void* stream) {
+  if (num_rows < 1) return MP4X_E_BADARG;
+  return moe_combine_launch(dtype, rows, num_rows, slots, weights, T, K, width, out, stream);
 }

@@ -19,6 +19,14 @@ local expert's two-layer MLP on its ``expert_counts`` slice -> combine with the 
 With an expert capacity (``capacity`` / ``capacity_factor``, see ``dispatchTokens``) the assignments
 past an expert's first C are clipped inside the dispatch: their slots are -1 in the plan, so both
 backward passes leave them out exactly as the forward did.
+
+With a per-source share (``source_capacity=S``, the padded fixed-capacity layout of
+``dispatchTokens``) the dispatched rows are ``[local experts, p*S, d]`` with zero rows behind every
+source's kept rows, and the layer's experts run as two batched GEMMs over that tensor.  Both backward
+passes follow the plan: the dispatch's is the unit-weight combine (pad rows are never read), the
+combine's is the padded scatter with the gate weights as ``row_scale`` (pad rows of the gradient are
+zero, so they add exactly zero to every expert-weight gradient).  Forward only can be captured
+(``comm.device.capture``); capturing autograd is out of scope.
 """
 from __future__ import annotations
 
@@ -32,16 +40,16 @@ from ..operators import Operators
 
 class _Dispatch(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, comm, expert_ids, num_experts, operand, capacity, capacity_factor):
+    def forward(ctx, x, comm, expert_ids, num_experts, operand, capacity, capacity_factor, source_capacity):
         rows, plan = comm.dispatchTokens(x.contiguous(), expert_ids, num_experts, operand=operand, capacity=capacity,
-                                         capacityFactor=capacity_factor)
+                                         capacityFactor=capacity_factor, sourceCapacity=source_capacity)
         ctx.comm, ctx.plan, ctx.operand = comm, plan, operand
         return rows, plan
 
     @staticmethod
     def backward(ctx, g_rows, _plan=None):
         gx = ctx.comm.combineTokens(g_rows.contiguous(), ctx.plan, None, operand=ctx.operand)
-        return gx, None, None, None, None, None, None
+        return gx, None, None, None, None, None, None, None
 
 
 class _Combine(torch.autograd.Function):
@@ -63,7 +71,7 @@ class _Combine(torch.autograd.Function):
         if weights is not None and ctx.needs_input_grad[1]:
             T, K = plan.num_tokens, plan.top_k
             sl = plan.slots.view(T, K)
-            if back.shape[0]:
+            if back.shape[0] and T:          # (a padded plan has rows even for a rank with no token)
                 y = back.reshape(back.shape[0], -1)[sl.clamp(min=0)].to(torch.float32)      # [T, K, H]
                 g_w = (g.reshape(T, 1, -1).to(torch.float32) * y).sum(-1)
                 g_w = torch.where(sl >= 0, g_w, torch.zeros_like(g_w)).view_as(weights)
@@ -73,11 +81,12 @@ class _Combine(torch.autograd.Function):
 
 
 def dispatch_tokens(comm, x: torch.Tensor, expert_ids: torch.Tensor, num_experts: int, operand=None, capacity=None,
-                    capacity_factor=None):
-    """Differentiable ``comm.dispatchTokens``: ``(rows, plan)``.  With an expert capacity a clipped
-    assignment has slot -1 in the plan: it takes no part in either backward pass (no gradient
-    reaches its token through it, and its gate weight's gradient is 0)."""
-    return _Dispatch.apply(x, comm, expert_ids, num_experts, operand, capacity, capacity_factor)
+                    capacity_factor=None, source_capacity=None):
+    """Differentiable ``comm.dispatchTokens``: ``(rows, plan)``.  With an expert capacity, or a
+    per-source share (``source_capacity``: the padded layout, ``rows`` ``[E/p, p*S, ...]``), a
+    clipped assignment has slot -1 in the plan: it takes no part in either backward pass (no
+    gradient reaches its token through it, and its gate weight's gradient is 0)."""
+    return _Dispatch.apply(x, comm, expert_ids, num_experts, operand, capacity, capacity_factor, source_capacity)
 
 
 def combine_tokens(comm, expert_rows: torch.Tensor, plan, weights: Optional[torch.Tensor] = None, operand=None):
@@ -97,10 +106,16 @@ class ExpertParallelMoE(torch.nn.Module):
 
     ``capacity_factor``: every expert accepts the first ``max(1, ceil(f * N / E))`` of the step's N
     assignments (all ranks') in (rank, token, k) order; the others are dropped (``dispatchTokens``).
-    ``last_plan`` is the last forward's plan (``clipped``, ``demand_matrix``), None before it."""
+    ``last_plan`` is the last forward's plan (``clipped``, ``demand_matrix``), None before it.
+
+    ``source_capacity`` (excludes ``capacity_factor``): every rank sends at most S of its
+    assignments to every expert, its first in (token, k) order, in the padded layout of
+    ``dispatchTokens(sourceCapacity=S)``: no host synchronisation in the step, and the local experts
+    run as two batched GEMMs (``baddbmm`` over ``[local experts, p*S, d_model]``, ReLU between them)
+    instead of a ragged loop.  ``last_plan.kept`` / ``valid`` / ``dropped`` stay on the device."""
 
     def __init__(self, comm, d_model: int, d_hidden: int, num_experts: int, top_k: int, seed: int = 0,
-                 device=None, dtype=torch.float32, operand=None, capacity_factor=None):
+                 device=None, dtype=torch.float32, operand=None, capacity_factor=None, source_capacity=None):
         super().__init__()
         p, r = comm.getSlaveNum(), comm.getRank()
         if num_experts % p:
@@ -108,7 +123,9 @@ class ExpertParallelMoE(torch.nn.Module):
         if not 1 <= top_k <= num_experts:
             raise ValueError("top_k must be in [1, num_experts]")
         self.comm, self.num_experts, self.top_k, self.operand = comm, num_experts, top_k, operand
-        self.capacity_factor, self.last_plan = capacity_factor, None
+        if source_capacity is not None and capacity_factor is not None:
+            raise ValueError("give source_capacity or capacity_factor, not both")
+        self.capacity_factor, self.source_capacity, self.last_plan = capacity_factor, source_capacity, None
         self.local_experts = num_experts // p
         self.first_expert = r * self.local_experts
         full = self.init_weights(d_model, d_hidden, num_experts, seed)
@@ -143,8 +160,14 @@ class ExpertParallelMoE(torch.nn.Module):
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         w, ids = self.route(x)
         rows, plan = dispatch_tokens(self.comm, x, ids, self.num_experts, self.operand,
-                                     capacity_factor=self.capacity_factor)
+                                     capacity_factor=self.capacity_factor, source_capacity=self.source_capacity)
         self.last_plan = plan
+        if self.source_capacity is not None:
+            # [el, p*S, d]: one pair of batched GEMMs whatever the ids were (a pad row's output is the
+            # biases' and is never read back; its gradient row is zero)
+            h = torch.relu(torch.baddbmm(self.b1.unsqueeze(1), rows, self.w1))
+            y = torch.baddbmm(self.b2.unsqueeze(1), h, self.w2)
+            return combine_tokens(self.comm, y, plan, w.contiguous(), self.operand)
         outs, off = [], 0
         for e, c in enumerate(plan.expert_counts):
             h = torch.relu(rows[off:off + c] @ self.w1[e] + self.b1[e])

@@ -557,6 +557,95 @@ def moe_combine(rows: torch.Tensor, slots: torch.Tensor, weights: Optional[torch
     return out
 
 
+def _moe_share(fn: str, nb: int, cap) -> int:
+    if isinstance(cap, bool) or not isinstance(cap, int) or cap < 1 or cap > (2 ** 31 - 1) // nb:
+        raise ValueError(f"{fn}: the share {cap!r} is not an int in [1, {(2 ** 31 - 1) // nb}]")
+    return cap
+
+
+def moe_route_scatter_pad(rc: RouteCount, x: torch.Tensor, top_k: int, out_rows: torch.Tensor, cap: int,
+                          row_scale: Optional[torch.Tensor] = None, stream=None) -> torch.Tensor:
+    """K9's scatter into the padded fixed-capacity layout after :func:`moe_route_count`: expert e
+    owns rows ``[e * cap, (e + 1) * cap)`` of ``out_rows`` (exactly ``nb * cap`` rows).  The
+    ``pe``-th assignment of expert e gets ``slots[a] = e * cap + pe`` iff ``pe < cap``, else -1 (as
+    do a negative id and an id >= nb); ``out_rows[slots[a]] = x[t]`` (times ``row_scale[a]``), and
+    every other row of ``out_rows`` is written as zeros, each row exactly once.  Every shape is
+    known before the ids are: nothing is read back, nothing is copied to the device."""
+    ids = rc.ids
+    n = ids.numel()
+    _dev_check(ids, x, out_rows, row_scale)
+    _, rb = _moe_rows("moe_route_scatter_pad", x)
+    cap = _moe_share("moe_route_scatter_pad", rc.nb, cap)
+    if top_k < 1 or x.shape[0] * top_k != n:
+        raise ValueError(f"moe_route_scatter_pad: {x.shape[0]} rows x top_k {top_k} != {n} ids")
+    if out_rows.dtype != x.dtype or tuple(out_rows.shape[1:]) != tuple(x.shape[1:]):
+        raise ValueError("moe_route_scatter_pad: out_rows dtype / row shape differ from x")
+    if out_rows.shape[0] != rc.nb * cap:
+        raise ValueError(f"moe_route_scatter_pad: out_rows holds {out_rows.shape[0]} rows, not {rc.nb} x {cap}")
+    if row_scale is not None and (row_scale.dtype != torch.float32 or row_scale.numel() != n):
+        raise ValueError("moe_route_scatter_pad: row_scale must be float32, one per assignment")
+    slots = torch.empty(n, dtype=torch.int64, device=ids.device)
+    check(native.hip().mp4x_moe_route_scatter_pad(
+        int(dtype_of_torch(x.dtype)), ids.data_ptr() if n else None, int(ids.dtype == torch.int64),
+        x.data_ptr() if n else None, row_scale.data_ptr() if row_scale is not None and n else None, n, int(top_k), rb,
+        rc.nb, cap, out_rows.data_ptr(), slots.data_ptr() if n else None, rc.scratch.data_ptr() if n else None,
+        rc.scratch.numel() if n else 0, stream_ptr(stream)), "mp4x_moe_route_scatter_pad")
+    return slots
+
+
+def moe_pad_counts(rc: RouteCount, cap: int, group: Optional[int] = None, group_pad: Optional[int] = None,
+                   kept: Optional[torch.Tensor] = None, stream=None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """``(kept, dropped)`` of the padded layout after :func:`moe_route_count`: ``kept[e] =
+    min(count of e, cap)`` and ``dropped`` int64 [3] = assignments past their share | negative ids |
+    ids >= nb, both on the ids' device and never read here.  ``group`` / ``group_pad``: ``kept`` is
+    laid out ``[nb / group, group_pad]`` (zero padding) instead of ``[nb]``; ``kept``: write there."""
+    ids = rc.ids
+    cap = _moe_share("moe_pad_counts", rc.nb, cap)
+    el = rc.nb if group is None else int(group)
+    el_pad = el if group_pad is None else int(group_pad)
+    if el < 1 or rc.nb % el or el_pad < el:
+        raise ValueError(f"moe_pad_counts: groups of {el} (padded to {el_pad}) do not tile {rc.nb} experts")
+    size = rc.nb // el * el_pad
+    if kept is None:
+        kept = torch.empty(size, dtype=torch.int64, device=ids.device)
+    _dev_check(ids, kept)
+    if kept.dtype != torch.int64 or kept.numel() != size:
+        raise ValueError(f"moe_pad_counts: kept must be int64 [{size}]")
+    dropped = torch.empty(3, dtype=torch.int64, device=ids.device)
+    n = ids.numel()
+    check(native.hip().mp4x_moe_pad_counts(n, rc.nb, cap, el, el_pad, kept.data_ptr(), dropped.data_ptr(),
+                                           rc.scratch.data_ptr() if n else None, rc.scratch.numel() if n else 0,
+                                           stream_ptr(stream)), "mp4x_moe_pad_counts")
+    return kept, dropped
+
+
+def moe_combine_rows(rows: torch.Tensor, slots: torch.Tensor, weights: Optional[torch.Tensor], num_tokens: int,
+                     top_k: int, out: Optional[torch.Tensor] = None, stream=None):
+    """:func:`moe_combine` over the padded layout: the slots index ``rows`` anywhere (the scatter
+    that made them bounds them by ``rows.shape[0]`` = nb * cap by construction), so nothing is read
+    back for a bounds check.  Rows no slot names are never read."""
+    _dev_check(rows, slots, weights, out)
+    width, _ = _moe_rows("moe_combine_rows", rows)
+    n = num_tokens * top_k
+    if slots.dtype != torch.int64 or slots.numel() != n or top_k < 1:
+        raise ValueError("moe_combine_rows: slots must be int64, num_tokens * top_k of them")
+    if weights is not None and (weights.dtype != torch.float32 or weights.numel() != n):
+        raise ValueError("moe_combine_rows: weights must be float32, one per assignment")
+    if rows.shape[0] < 1:
+        raise ValueError("moe_combine_rows: no rows")
+    if out is None:
+        out = torch.empty((num_tokens,) + tuple(rows.shape[1:]), dtype=rows.dtype, device=rows.device)
+    elif out.dtype != rows.dtype or tuple(out.shape) != (num_tokens,) + tuple(rows.shape[1:]):
+        raise ValueError("moe_combine_rows: out dtype / shape mismatch")
+    if n == 0:
+        return out
+    check(native.hip().mp4x_moe_combine_rows(int(dtype_of_torch(rows.dtype)), rows.data_ptr(), rows.shape[0],
+                                             slots.data_ptr(), weights.data_ptr() if weights is not None else None,
+                                             num_tokens, int(top_k), width, out.data_ptr(), stream_ptr(stream)),
+          "mp4x_moe_combine_rows")
+    return out
+
+
 # int64 key sorts: rocPRIM's own dispatch (block sort + merge passes below 1 M items, whatever the
 # key width) or forced onesweep (csrc/kernels/sparse.hip OnesweepSort: ~27 us per 8-bit pass at
 # 200 k items).  Measured on MI355X (profiles/r6/sparse/sort_ab.jsonl): onesweep wins at <= 16 bits

@@ -29,6 +29,25 @@ its expert with that quota and gives a clipped assignment slot -1.  A capped cal
 the uncapped call on the ids with every clipped assignment replaced by -1: clipped rows are never
 read, written or sent, every later combine skips them, and both backward passes follow the plan.
 
+Padded fixed-capacity layout (``source_capacity=S``): every source rank may send at most S rows to
+every expert, its first S in assignment order, so every buffer of the step has a shape known before
+the ids are seen and nothing leaves the device between the router and the combined output: no
+count exchange, no host sync, and the pair can be recorded by ``DeviceEngine.capture``.
+
+* send buffer ``[E*S, ...]``: the ``pe``-th of this rank's assignments with expert e sits in row
+  ``e*S + pe`` iff ``pe < S`` (``slots[a]``, else -1); the rows ``[min(cnt[e], S), S)`` of every
+  expert block are zeros.  Every row is written exactly once per call (the scatter, then a fill of
+  the pad rows; no memset of the buffer).
+* the exchange is the all-to-all with the constant count ``el*S`` (``el = E/p``): one copy plan on
+  the IPC mesh that carries the rows and the ``kept`` counts together, else two equal-split
+  ``all_to_all_single``.  Rank r returns ``rows [el, p*S, ...]``: ``rows[e, i*S + j]`` is source i's
+  j-th kept row of expert ``r*el + e`` or zeros, and ``plan.valid[e, i]`` says how many are rows.
+* the way back is the inverse regroup and the same fixed exchange, which lands ``[E*S, ...]`` in slot
+  order; the combine reads it through ``slots`` and never reads a pad row.
+
+A padded dispatch -> experts -> combine is, bit for bit, the uncapped call on the ids with every
+assignment past its per-(rank, expert) share replaced by -1 (``tests/moe_padded_ref.py``).
+
 GPU tensors run the K9 kernels (``csrc/kernels/moe.hip``); host tensors, and GPU tensors where
 the native library is absent, run the torch implementation of the same contract below.
 """
@@ -59,13 +78,23 @@ class TokenPlan:
     resolved C of the call (None: no capacity).  ``demand_matrix[i][e]``: the assignments of rank i
     with expert e before clipping (``expert_matrix`` itself when there is no capacity): what a
     load-balancing loss or a monitor wants.  ``clipped``: this rank's assignments the capacity
-    dropped, ``sum_e demand_matrix[r][e] - expert_matrix[r][e]``."""
+    dropped, ``sum_e demand_matrix[r][e] - expert_matrix[r][e]``.
+
+    A padded call (``source_capacity`` = its S, else None) knows its shapes without the ids:
+    ``expert_counts = (p*S,)*el``, ``send_counts = recv_counts = (el*S,)*p`` and ``matrix`` are
+    constants, ``slots[a] = e*S + pe`` or -1.  What the ids decide stays on the device and is never
+    read back by the library: ``kept`` int64 ``[E]`` (``min(cnt[e], S)`` on this rank), ``valid``
+    int64 ``[el, p]`` (source i's kept rows of local expert e: ``rows[e, i*S : i*S + valid[e, i]]``
+    are rows, the rest of the block zeros) and ``dropped`` int64 ``[3]`` (assignments past their
+    share, negative ids, ids >= E).  ``clipped``, ``demand_matrix`` and ``expert_matrix`` are None
+    there.  Inside a captured graph every replay rewrites ``slots``, ``kept``, ``valid``, ``dropped``."""
     __slots__ = ("num_tokens", "top_k", "num_experts", "expert_counts", "send_counts", "recv_counts", "slots",
                  "matrix", "expert_matrix", "row_shape", "dtype", "rank", "capacity", "demand_matrix", "clipped",
-                 "_route", "_clip", "_frozen")
+                 "source_capacity", "kept", "valid", "dropped", "_route", "_clip", "_frozen")
 
     def __init__(self, **kw):
-        kw = {"capacity": None, "demand_matrix": kw.get("expert_matrix"), "clipped": 0, "_clip": None, **kw}
+        kw = {"capacity": None, "demand_matrix": kw.get("expert_matrix"), "clipped": 0, "_clip": None,
+              "source_capacity": None, "kept": None, "valid": None, "dropped": None, **kw}
         for k, v in kw.items():
             object.__setattr__(self, k, v)
         object.__setattr__(self, "_frozen", True)
@@ -92,7 +121,7 @@ def _width(shape: Sequence[int]) -> int:
     return w
 
 
-def _check_rows(what: str, t: torch.Tensor):
+def _check_rows(what: str, t: torch.Tensor, padded: bool = False):
     if not isinstance(t, torch.Tensor):
         raise Mp4jException(f"{what} needs a torch tensor")
     if t.dim() < 1 or not t.is_contiguous():
@@ -102,7 +131,7 @@ def _check_rows(what: str, t: torch.Tensor):
     rb = _width(t.shape[1:]) * t.element_size()
     if rb == 0 or (t.is_cuda and rb % 16):
         raise Mp4jException(f"{what}: rows of {rb} bytes on a GPU tensor are not whole 16-byte vectors")
-    if t.is_cuda:
+    if t.is_cuda and not padded:          # the padded layout exchanges no counts: it may be captured
         from ..ops.native import capturing_now
         if capturing_now():
             raise Mp4jException(f"{what} inside a graph capture: the count exchange is a host sync")
@@ -262,11 +291,12 @@ def _route_rows(x: torch.Tensor, plan_route, top_k: int, placed: int, row_scale:
 
 
 def dispatch(engine, x: torch.Tensor, expert_ids: torch.Tensor, num_experts: int, operand=None, capacity=None,
-             capacity_factor=None):
+             capacity_factor=None, source_capacity=None):
     """``(rows, plan)``: see ``ProcessCommSlave.dispatchTokens``."""
     p, r = engine.p, engine.rank
     E = int(num_experts)
-    _check_rows("dispatchTokens", x)
+    _check_source_capacity(source_capacity, capacity, capacity_factor)
+    _check_rows("dispatchTokens", x, padded=source_capacity is not None)
     _check_capacity(capacity, capacity_factor)
     if E < 1 or E % p:
         raise Mp4jException(f"dispatchTokens: numExperts {E} is not a positive multiple of the {p} ranks")
@@ -282,6 +312,8 @@ def dispatch(engine, x: torch.Tensor, expert_ids: torch.Tensor, num_experts: int
     if K < 1:
         raise Mp4jException("dispatchTokens: expertIds needs at least one column")
     ids = expert_ids.reshape(-1).contiguous()
+    if source_capacity is not None:
+        return _dispatch_padded(engine, x, ids, T, K, E, source_capacity, operand)
     native = _native_ok(x)
     # 1. route count
     if native:
@@ -341,9 +373,14 @@ def dispatch_scaled(engine, x: torch.Tensor, plan: TokenPlan, row_scale: Optiona
     """Dispatch ``x`` [T, ...] again along ``plan`` with every assignment's row times
     ``row_scale`` [T, K] (the combine's backward w.r.t. the expert rows): the route scatter with
     the plan's scan, clipping and matrix, no count exchange."""
-    _check_rows("dispatchTokens", x)
+    _check_rows("dispatchTokens", x, padded=plan.source_capacity is not None)
     _check_plan_rows("dispatchTokens", x, plan, plan.num_tokens)
     row_scale = _check_weights(row_scale, plan, x)
+    if plan.source_capacity is not None:
+        send, _, _ = _pad_buffers(x, plan.num_experts, plan.source_capacity, len(plan.matrix), counts=False)
+        _pad_scatter(x, plan._route, plan.top_k, plan.num_experts, plan.source_capacity, row_scale, send)
+        got, _ = _pad_exchange(engine, send, None, None, operand)
+        return _pad_regroup(got, plan, inverse=False)
     send, _ = _route_rows(x, plan._route, plan.top_k, sum(plan.send_counts), row_scale, plan._clip)
     return _forward_rows(engine, send, plan, operand)
 
@@ -392,9 +429,211 @@ def combine(engine, expert_rows: torch.Tensor, plan: TokenPlan, weights=None, op
     """``out`` [T, ...]: see ``ProcessCommSlave.combineTokens``."""
     if not isinstance(plan, TokenPlan):
         raise Mp4jException("combineTokens: plan must be the TokenPlan dispatchTokens returned")
+    if plan.source_capacity is not None:
+        return _combine_padded(engine, expert_rows, plan, weights, operand, return_slot_rows)
     _check_rows("combineTokens", expert_rows)
+    if expert_rows.dim() >= 2 and tuple(expert_rows.shape[2:]) == plan.row_shape and \
+            tuple(expert_rows.shape[1:]) != plan.row_shape:
+        raise Mp4jException(f"combineTokens: rows {tuple(expert_rows.shape)} are in the padded [experts, rows, ...] "
+                            f"layout, the plan is a ragged one (no sourceCapacity)")
     _check_plan_rows("combineTokens", expert_rows, plan, plan.num_rows)
     weights = _check_weights(weights, plan, expert_rows)
     back = return_rows(engine, expert_rows, plan, operand)
     out = combine_local(back, plan, weights)
+    return (out, back) if return_slot_rows else out
+
+
+# ---------------------------------------------------------------- the padded fixed-capacity layout
+def _check_source_capacity(source_capacity, capacity, capacity_factor):
+    """The caller's contract, the same on every rank: refused before any work."""
+    if source_capacity is None:
+        return
+    if capacity is not None or capacity_factor is not None:
+        raise Mp4jException("dispatchTokens: sourceCapacity excludes capacity / capacityFactor (both need the demand "
+                            "matrix, which the padded layout never gathers)")
+    S = source_capacity
+    if isinstance(S, bool) or not isinstance(S, int) or S < 1:
+        raise Mp4jException(f"dispatchTokens: sourceCapacity {S!r} is not an int >= 1")
+
+
+def _torch_pad(ids: torch.Tensor, nb: int, S: int):
+    """The torch form of the padded route: (slots int64[n], kept int64[nb], dropped int64[3])."""
+    counts, slots, order = _torch_route(ids, nb)
+    start = torch.cumsum(counts[:nb], 0) - counts[:nb]
+    e = ids.to(torch.int64)[order]
+    pe = torch.arange(order.numel(), dtype=torch.int64, device=ids.device) - start[e]
+    stay = pe < S
+    slots = torch.full_like(slots, -1)
+    slots[order[stay]] = e[stay] * S + pe[stay]
+    kept = counts[:nb].clamp(max=S)
+    dropped = torch.stack([(counts[:nb] - kept).sum(), counts[nb], counts[nb + 1]])
+    return slots, kept, dropped
+
+
+def _torch_pad_scatter(x: torch.Tensor, slots: torch.Tensor, top_k: int, row_scale: Optional[torch.Tensor],
+                       out: torch.Tensor):
+    """``out[slots[a]] = x[a // K]`` (times ``row_scale[a]``), every other row zero."""
+    out.zero_()
+    a = torch.nonzero(slots >= 0).reshape(-1)
+    rows = x[a // top_k]
+    if row_scale is not None:
+        s = row_scale.reshape(-1)[a].view((-1,) + (1,) * (x.dim() - 1))
+        rows = (s * rows.to(torch.float32)).to(x.dtype)
+    out[slots[a]] = rows
+    return out
+
+
+def _pad_buffers(x: torch.Tensor, E: int, S: int, p: int, counts: bool = True):
+    """(send rows ``[E*S, ...]``, the counts' wire int64 ``[p, el_pad]`` or None, el_pad).  On a GPU
+    both are views of ONE allocation, rows first: the copy plan stages them from one base address.
+    Every destination's counts start on a 16-byte boundary (el_pad = el rounded up to even)."""
+    el = E // p
+    el_pad = el + (el & 1)
+    shape = (E * S,) + tuple(x.shape[1:])
+    if not x.is_cuda:
+        wire = torch.empty((p, el_pad), dtype=torch.int64) if counts else None
+        return torch.empty(shape, dtype=x.dtype), wire, el_pad
+    nbytes = E * S * _width(x.shape[1:]) * x.element_size()             # a multiple of 16 (_check_rows)
+    whole = torch.empty(nbytes + (p * el_pad * 8 if counts else 0), dtype=torch.uint8, device=x.device)
+    send = whole[:nbytes].view(x.dtype).view(shape)
+    wire = whole[nbytes:].view(torch.int64).view(p, el_pad) if counts else None
+    return send, wire, el_pad
+
+
+def _pad_scatter(x, route, top_k: int, E: int, S: int, row_scale, send):
+    """The padded route scatter into ``send``; returns the slots."""
+    if _native_ok(x):
+        from ..ops.device_ops import moe_route_scatter_pad
+        return moe_route_scatter_pad(route, x, top_k, send, S, row_scale=row_scale)
+    _torch_pad_scatter(x, route, top_k, row_scale, send)
+    return route
+
+
+def _pad_ipc_inst(engine, like: torch.Tensor, need_bytes: int):
+    """The IPC instance that runs a padded exchange of ``need_bytes`` per rank as one copy plan, or
+    None (two equal-split all-to-alls).  The padded path's own qualification, every condition
+    rank-independent: the environment, the device kind, the mesh, the payload inside one staging
+    instance, and inside a capture an instance with device epochs (``IpcAllreduce._vec_ok``'s rule)."""
+    from . import sparse
+    from ..ops.native import capturing_now
+    if not (sparse._SPARSE_IPC and like.is_cuda and engine.p > 1 and getattr(engine, "ipc_enabled", False)
+            and engine.coll.__class__.__name__ == "TorchColl" and engine.algo in ("", "auto", "ipc")):
+        return None
+    if engine.ipc() is None:
+        return None
+    inst = sparse._ipc_inst(engine, need_bytes)
+    if inst is None or (capturing_now() and inst._epoch_dev is None):
+        return None
+    return inst
+
+
+def _pad_exchange(engine, send: torch.Tensor, wire: Optional[torch.Tensor], el_pad, operand):
+    """The all-to-all with the constant count: block j of ``send`` (``rows / p`` rows) goes to rank
+    j, and so does row j of ``wire`` (int64 ``[p, el_pad]``, the kept counts) when given.  Returns
+    (rows in source order, the received counts or None).  One stream, no host sync."""
+    p, r = engine.p, engine.rank
+    if p == 1:
+        return send, wire
+    from ..ops.native import capturing_now
+    n = send.shape[0]
+    shape = tuple(send.shape)
+    if send.is_cuda and operand is not None and not capturing_now():
+        # the caller's operand (a wire codec) is the exact all-to-all's business, as in the ragged call
+        got, _ = engine.all_to_all_v(send, [n // p] * p, None, operand, mat=[[n // p] * p] * p)
+        got_wire = None
+        if wire is not None:
+            got_wire = torch.empty_like(wire)
+            engine.coll.all_to_all_single(got_wire, wire)
+        return got, got_wire
+    nbytes = send.numel() * send.element_size()
+    cbytes = wire.numel() * 8 if wire is not None else 0
+    inst = _pad_ipc_inst(engine, send, nbytes + cbytes)
+    if inst is not None:
+        # One copy plan.  The plan's barriers are per block: block b of a rank may pull only what
+        # block b of the peer staged, so a pull must start where a stage item starts (the same
+        # relative index on both sides).  Hence one stage item per destination's rows (the own
+        # block never crosses the mesh: a local copy), and the counts as ONE region that every rank
+        # pulls whole from every peer (p * el_pad numbers), taking its own row of it afterwards:
+        # p stage items and 2p - 1 pulls for any p the mesh allows.
+        if wire is not None and wire.data_ptr() != send.data_ptr() + nbytes:
+            raise Mp4jException("padded exchange: the counts do not follow the rows (see _pad_buffers)")
+        rv, mv, cv = nbytes // 16, nbytes // 16 // p, cbytes // 16
+        out = torch.empty(nbytes + p * cbytes, dtype=torch.uint8, device=send.device)
+        stage = [(j * mv, j * mv, mv, 0) for j in range(p) if j != r] + ([(rv, rv, cv, 0)] if cv else [])
+        pulls = [(r * mv, j * mv, mv, j) for j in range(p) if j != r]
+        if cv:
+            pulls += [(rv, rv + j * cv, cv, j) for j in range(p)]
+        inst._plan(stage, pulls, send.data_ptr(), out.data_ptr(), mv)
+        engine._count("all_to_all_v.ipc.padded")
+        got = out[:nbytes].view(send.dtype).view(shape)
+        got[r * (n // p):(r + 1) * (n // p)].copy_(send[r * (n // p):(r + 1) * (n // p)])
+        return got, (out[nbytes:].view(torch.int64).view(p, p, el_pad)[:, r] if wire is not None else None)
+    # equal splits: RCCL (capturable) on GPU tensors, bytes over the host backend otherwise
+    raw = send.reshape(p, -1).view(torch.uint8)
+    got = torch.empty_like(raw)
+    engine.coll.all_to_all_single(got, raw)
+    got_wire = None
+    if wire is not None:
+        got_wire = torch.empty_like(wire)
+        engine.coll.all_to_all_single(got_wire, wire.contiguous())
+    return got.view(send.dtype).view(shape), got_wire
+
+
+def _pad_regroup(rows: torch.Tensor, plan: TokenPlan, inverse: bool) -> torch.Tensor:
+    """``[p, el, S] -> [el, p*S]`` (or back, to ``[E*S]`` rows): one fixed strided copy; with one
+    local expert or one rank the two orders coincide and the result is a view."""
+    p = len(plan.matrix)
+    el, S = plan.num_experts // p, plan.source_capacity
+    if inverse:
+        if el == 1 or p == 1:
+            return rows.view((p * el * S,) + plan.row_shape)
+        return rows.view((el, p, S) + plan.row_shape).transpose(0, 1).contiguous().view((p * el * S,) + plan.row_shape)
+    if el == 1 or p == 1:
+        return rows.view((el, p * S) + plan.row_shape)
+    return rows.view((p, el, S) + plan.row_shape).transpose(0, 1).contiguous().view((el, p * S) + plan.row_shape)
+
+
+def _dispatch_padded(engine, x: torch.Tensor, ids: torch.Tensor, T: int, K: int, E: int, S: int, operand):
+    p, r = engine.p, engine.rank
+    el = E // p
+    engine._count("moe.dispatch.padded")
+    send, wire, el_pad = _pad_buffers(x, E, S, p)
+    if _native_ok(x):
+        from ..ops.device_ops import moe_pad_counts, moe_route_count
+        route = moe_route_count(ids, E)
+        _, dropped = moe_pad_counts(route, S, group=el, group_pad=el_pad, kept=wire.view(-1))
+        slots = _pad_scatter(x, route, K, E, S, None, send)
+    else:
+        slots, kept, dropped = _torch_pad(ids, E, S)
+        wire.zero_()
+        wire[:, :el] = kept.view(p, el)
+        route = slots
+        _torch_pad_scatter(x, slots, K, None, send)
+    const = (el * S,) * p
+    got, got_wire = _pad_exchange(engine, send, wire, el_pad, operand)
+    plan = TokenPlan(num_tokens=T, top_k=K, num_experts=E, expert_counts=(p * S,) * el, send_counts=const,
+                     recv_counts=const, slots=slots, matrix=(const,) * p, expert_matrix=None, demand_matrix=None,
+                     clipped=None, row_shape=tuple(x.shape[1:]), dtype=x.dtype, rank=r, source_capacity=S,
+                     kept=wire[:, :el].reshape(E), valid=got_wire[:, :el].t().contiguous(), dropped=dropped,
+                     _route=route)
+    return _pad_regroup(got, plan, inverse=False), plan
+
+
+def _combine_padded(engine, expert_rows: torch.Tensor, plan: TokenPlan, weights, operand, return_slot_rows):
+    p = len(plan.matrix)
+    el, S = plan.num_experts // p, plan.source_capacity
+    want = (el, p * S) + plan.row_shape
+    if not isinstance(expert_rows, torch.Tensor) or tuple(expert_rows.shape) != want:
+        raise Mp4jException(f"combineTokens: the plan is a padded one (sourceCapacity {S}): rows must be "
+                            f"{want}, not {tuple(getattr(expert_rows, 'shape', ()))}")
+    if not expert_rows.is_contiguous() or expert_rows.dtype != plan.dtype or expert_rows.device != plan.slots.device:
+        raise Mp4jException(f"combineTokens: rows must be contiguous {plan.dtype} on {plan.slots.device}")
+    weights = _check_weights(weights, plan, expert_rows)
+    back, _ = _pad_exchange(engine, _pad_regroup(expert_rows, plan, inverse=True), None, None, operand)
+    T, K = plan.num_tokens, plan.top_k
+    if _native_ok(back):
+        from ..ops.device_ops import moe_combine_rows
+        out = moe_combine_rows(back, plan.slots, weights, T, K)
+    else:
+        out = _torch_combine(back, plan.slots, weights, T, K)
     return (out, back) if return_slot_rows else out

@@ -947,7 +947,7 @@ class ProcessCommSlave:
         return self.device.all_to_all_v(sendData, list(sendCounts), recvData, operand)
 
     def dispatchTokens(self, x, expertIds, numExperts: int, operand: Optional[Operand] = None, capacity=None,
-                       capacityFactor=None):
+                       capacityFactor=None, sourceCapacity=None):
         """Expert-parallel token dispatch (extension, over ``alltoallArray``'s transport).
 
         ``x`` is ``[T, ...]`` (contiguous; f32 / bf16 / f16), ``expertIds`` ``[T, K]`` or ``[T]``
@@ -983,17 +983,39 @@ class ProcessCommSlave:
         ``plan.demand_matrix`` the unclipped ``D`` (``plan.expert_matrix`` holds what stayed) and
         ``plan.clipped`` this rank's clipped assignments.
 
+        Padded fixed-capacity layout: ``sourceCapacity`` (an int ``S >= 1``, the same on every
+        rank).  Every source rank may send at most S rows to every expert: the ``pe``-th of this
+        rank's assignments with expert e (in ``t*K + k`` order) stays iff ``pe < S``, at
+        ``plan.slots[a] = e*S + pe``; the others, like a negative id, get -1.  Every shape of the
+        step is then known before the ids are: the send buffer is ``[E*S, ...]`` with zeros
+        behind every expert's kept rows, the exchange moves the constant ``(E/p)*S`` rows per
+        peer, and ``rows`` comes back as ``[E/p, p*S, ...]``: ``rows[e, i*S + j]`` is source i's
+        j-th kept row of local expert e, or all-zero bits.  There is no count exchange and no
+        host synchronisation, so the call (and :meth:`combineTokens` along its plan) may run
+        inside ``comm.device.capture`` and be replayed on fresh ids.  What the ids decide stays
+        on the device: ``plan.kept`` ``[E]``, ``plan.valid`` ``[E/p, p]`` (how many rows of
+        every source's block are real) and ``plan.dropped`` ``[3]`` (past the share, negative,
+        ``>= E``); ``plan.clipped``, ``plan.demand_matrix`` and ``plan.expert_matrix`` are None.
+        An id ``>= E`` cannot raise here, since seeing it would need the synchronisation the
+        layout exists to avoid: it gets slot -1 and is counted in ``plan.dropped[2]``.  The
+        result equals, bit for bit, the uncapped call on the ids with every assignment past its
+        per-(rank, expert) share set to -1.  ``sourceCapacity`` excludes ``capacity`` and
+        ``capacityFactor`` (both need the demand matrix); ``operand`` goes to the exact
+        all-to-all with the constant count matrix outside a capture.
+
         Raises :class:`Mp4jException`, on every rank alike and before any row moves, for ``E``
         not a multiple of the rank count or above 2048, mismatched shapes, an id ``>= E`` on any
         rank (the message names the rank), another dtype, GPU rows that are not whole 16-byte
         vectors, both ``capacity`` and ``capacityFactor``, a ``capacity`` that is not an int
         ``>= 1`` (a bool is refused), a ``capacityFactor`` that is not a finite number ``> 0``,
-        and a call inside a graph capture (the count exchange is a host sync)."""
+        a ``sourceCapacity`` that is not an int ``>= 1`` or that comes with a capacity, and,
+        without ``sourceCapacity``, a call inside a graph capture (the count exchange is a host
+        sync)."""
         self._tick("dispatchTokens")
         if not _is_torch(x):
             raise Mp4jException("dispatchTokens needs a torch tensor (device engine)")
         return self.device.dispatch_tokens(x, expertIds, numExperts, operand, capacity=capacity,
-                                           capacity_factor=capacityFactor)
+                                           capacity_factor=capacityFactor, source_capacity=sourceCapacity)
 
     def combineTokens(self, expertRows, plan, weights=None, operand: Optional[Operand] = None,
                       returnSlotRows: bool = False):
@@ -1007,9 +1029,14 @@ class ProcessCommSlave:
         bit the CPU form's.  ``returnSlotRows``: also return the rows as they came back, in the
         sender's slot order (``plan.slots``), which the weights' gradient needs.
 
+        Along a padded plan (``dispatchTokens(sourceCapacity=S)``) ``expertRows`` is
+        ``[E/p, p*S, ...]``: the inverse regroup and the same fixed exchange land ``[E*S, ...]``
+        in slot order, pad rows are never read, and the call may be captured.
+
         Raises :class:`Mp4jException` for weights that are not float32 ``[T, K]``, rows that do
-        not match the plan (``expertRows.shape[0] != sum(plan.expert_counts)``, dtype, row shape)
-        and a call inside a graph capture."""
+        not match the plan (``expertRows.shape[0] != sum(plan.expert_counts)``, dtype, row shape;
+        ragged rows along a padded plan and padded rows along a ragged one) and, along a ragged
+        plan, a call inside a graph capture."""
         self._tick("combineTokens")
         if not _is_torch(expertRows):
             raise Mp4jException("combineTokens needs a torch tensor (device engine)")

@@ -354,7 +354,13 @@ def _ipc_rows_alltoallv(engine, rows: torch.Tensor, mat: List[List[int]]):
         return None
     n = sum(mat[r])
     src = rows if rows.data_ptr() % 16 == 0 else rows.clone()
-    stage = [(0, 0, n * v, 0)] if n else []
+    # one stage item per destination: the plan's barriers are per block, so a peer's pull has to
+    # start where a stage item starts (block b then pulls exactly what block b staged)
+    stage, s0 = [], 0
+    for j in range(p):
+        if mat[r][j]:
+            stage.append((s0 * v, s0 * v, mat[r][j] * v, 0))
+        s0 += mat[r][j]
     pulls, off = [], 0
     for j in range(p):
         s0 = sum(mat[j][:r])                      # rank j's block for this rank, in its buffer
