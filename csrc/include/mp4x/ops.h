@@ -217,6 +217,35 @@ int mp4x_moe_pad_counts(int64_t n, int nb, int64_t cap, int el, int el_pad, int6
 int mp4x_moe_combine_rows(int dtype, const void* rows, int64_t num_rows, const int64_t* slots, const float* weights,
                           int64_t T, int K, int64_t width, void* out, void* stream);
 
+// ---------------------------------------------------------------- K10 fused top-k router gate
+// logits[T][E], contiguous, f32 / bf16 / f16 (else MP4X_E_UNSUPPORTED), 16-byte aligned; 1 <= E <=
+// 2048, 1 <= K <= min(E, 16), 0 <= T <= INT32_MAX / 2 / K, else MP4X_E_BADARG, as is a null or
+// misaligned pointer (weights, lse, prob_sum, g_*: 4 bytes; ids: 4 or 8 by ids_are_i64; counts: 8;
+// scratch: 256).  Every refusal comes before any launch.  All arithmetic is f32 on the exactly
+// converted logits.  Deterministic: no floating-point atomics, no global atomics.
+// Forward: ids[t][k] (int32 or int64 by ids_are_i64), k = 0 .. K-1, are the first K columns of row t
+// in the order (logit descending, column ascending; -0 == +0; -inf last), always distinct and inside
+// [0, E) whatever the bits of the row are; lse[t] = m + log(sum_j exp(l_j - m)), m the row maximum;
+// weights[t][k] = p[ids[t][k]], p_j = exp(l_j - m) / sum, divided by the sum of the K chosen p (added
+// in k order) when renormalize != 0.  prob_sum (f32[E]) and counts (int64[E]), both or neither:
+// prob_sum[e] = sum_t p[t][e] in a fixed order, counts[e] = the number of ids equal to e; they need
+// scratch of mp4x_moe_gate_scratch_bytes(dtype, T, E) bytes (0 for arguments the forward refuses),
+// which is not read without them.  T == 0 launches nothing, or with the statistics writes their zeros.
+size_t mp4x_moe_gate_scratch_bytes(int dtype, int64_t T, int E);
+int mp4x_moe_gate_topk(int dtype, const void* logits, int64_t T, int E, int K, int renormalize, float* weights,
+                       void* ids, int ids_are_i64, float* lse, float* prob_sum, int64_t* counts, void* scratch,
+                       size_t scratch_bytes, void* stream);
+// Backward from the saved logits, lse and ids (nothing else of size [T][E] is kept): with p_j =
+// exp(l_j - lse[t]) and s = the sum of the K chosen p in k order,
+//   gq_k = g_weights[t][k], or (g_weights[t][k] - sum_k' g_weights[t][k'] * p_k' / s) / s when renormalize,
+//   gp_j = g_prob_sum[j] + sum_k [ids[t][k] == j] gq_k,  dot = sum_j gp_j * p_j,
+//   g_logits[t][j] = round_to_dtype(p_j * (gp_j - dot) + g_lse[t] * p_j).
+// g_weights (f32[T][K]), g_lse (f32[T]) and g_prob_sum (f32[E]) may each be NULL: zeros.  g_logits has
+// the logits' dtype and alignment.  An id outside [0, E) takes no part (never an address).  T == 0 is 0.
+int mp4x_moe_gate_backward(int dtype, const void* logits, const float* lse, const void* ids, int ids_are_i64, int64_t T,
+                           int E, int K, int renormalize, const float* g_weights, const float* g_lse,
+                           const float* g_prob_sum, void* g_logits, void* stream);
+
 // ---------------------------------------------------------------- errors
 // Reads and clears this thread's last HIP error.  mp4x reports its own failures through return
 // codes; a failed HIP call must not stay "last error" for PyTorch's next kernel-launch check to

@@ -30,7 +30,7 @@ zero, so they add exactly zero to every expert-weight gradient).  Forward only c
 """
 from __future__ import annotations
 
-from typing import Dict, Optional
+from typing import Dict, NamedTuple, Optional
 
 import torch
 
@@ -94,6 +94,125 @@ def combine_tokens(comm, expert_rows: torch.Tensor, plan, weights: Optional[torc
     return _Combine.apply(expert_rows, weights, comm, plan, operand)
 
 
+# ---------------------------------------------------------------- the router gate (K10)
+GATE_MAX_EXPERTS, GATE_MAX_TOP_K = 2048, 16      # csrc/kernels/moe_gate.hip: kGateMaxE, kGateMaxK
+
+
+class GateResult(NamedTuple):
+    """What :func:`route_topk` returns.  ``weights`` float32 [T, K], ``lse`` float32 [T] and
+    ``prob_sum`` float32 [E] are differentiable; ``ids`` [T, K] and ``counts`` int64 [E] are not.
+    ``prob_sum`` and ``counts`` are None without ``stats``."""
+    weights: torch.Tensor
+    ids: torch.Tensor
+    lse: torch.Tensor
+    prob_sum: Optional[torch.Tensor]
+    counts: Optional[torch.Tensor]
+
+
+def _sum_in_k_order(q: torch.Tensor) -> torch.Tensor:
+    s = q[:, 0]
+    for k in range(1, q.shape[1]):
+        s = s + q[:, k]
+    return s
+
+
+def gate_forward_torch(logits: torch.Tensor, top_k: int, renormalize: bool, ids_dtype, stats: bool):
+    """The definition of the gate in torch (float32 on the exactly converted logits): what K10
+    computes, for host tensors and for shapes outside the kernel's range."""
+    lg = logits.to(torch.float32)
+    T, E = lg.shape
+    # (logit descending, index ascending): the stable sort keeps equal logits in index order
+    ids = torch.sort(lg, dim=-1, descending=True, stable=True).indices[:, :top_k]
+    m = lg.max(dim=-1, keepdim=True).values if T else lg.new_zeros((0, 1))
+    ex = torch.exp(lg - m)
+    total = ex.sum(dim=-1, keepdim=True)
+    lse = (m + torch.log(total)).squeeze(-1)
+    p = ex / total
+    w = p.gather(1, ids)
+    if renormalize:
+        w = w / _sum_in_k_order(w).unsqueeze(1)
+    prob_sum = counts = None
+    if stats:
+        prob_sum = p.sum(dim=0)
+        counts = torch.bincount(ids.reshape(-1), minlength=E)
+    return w, ids.to(ids_dtype), lse, prob_sum, counts
+
+
+def gate_backward_torch(logits: torch.Tensor, lse: torch.Tensor, ids: torch.Tensor, renormalize: bool,
+                        g_weights: Optional[torch.Tensor], g_lse: Optional[torch.Tensor],
+                        g_prob_sum: Optional[torch.Tensor]) -> torch.Tensor:
+    """The closed-form backward of the gate in torch, from the saved logits, lse and ids; an absent
+    gradient counts as zero.  One rounding to the logits' dtype."""
+    lg = logits.to(torch.float32)
+    ids = ids.to(torch.int64)
+    p = torch.exp(lg - lse.unsqueeze(1))
+    gp = torch.zeros_like(p) if g_prob_sum is None else g_prob_sum.unsqueeze(0).expand_as(p).clone()
+    if g_weights is not None:
+        gq = g_weights
+        if renormalize:
+            q = p.gather(1, ids)
+            s = _sum_in_k_order(q).unsqueeze(1)
+            gq = (g_weights - _sum_in_k_order(g_weights * (q / s)).unsqueeze(1)) / s
+        gp.scatter_add_(1, ids, gq)
+    dot = (gp * p).sum(dim=-1, keepdim=True)
+    g = p * (gp - dot)
+    if g_lse is not None:
+        g = g + g_lse.unsqueeze(1) * p
+    return g.to(logits.dtype)
+
+
+def _gate_is_fused(logits: torch.Tensor, top_k: int) -> bool:
+    return (logits.is_cuda and logits.dtype in (torch.float32, torch.bfloat16, torch.float16)
+            and 1 <= logits.shape[1] <= GATE_MAX_EXPERTS and top_k <= GATE_MAX_TOP_K)
+
+
+class _RouteTopK(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, logits, top_k, renormalize, ids_dtype, stats):
+        logits = logits.contiguous()
+        ctx.fused = _gate_is_fused(logits, top_k)
+        if ctx.fused:
+            from ..ops import device_ops
+            w, ids, lse, prob_sum, counts = device_ops.moe_gate_topk(logits, top_k, renormalize, ids_dtype, stats)
+        else:
+            w, ids, lse, prob_sum, counts = gate_forward_torch(logits, top_k, renormalize, ids_dtype, stats)
+        ctx.renormalize = renormalize
+        ctx.save_for_backward(logits, lse, ids)
+        ctx.set_materialize_grads(False)
+        ctx.mark_non_differentiable(*(t for t in (ids, counts) if t is not None))
+        return w, ids, lse, prob_sum, counts
+
+    @staticmethod
+    def backward(ctx, g_w, _g_ids, g_lse, g_psum, _g_counts):
+        logits, lse, ids = ctx.saved_tensors
+        g_w, g_lse, g_psum = (None if g is None else g.to(torch.float32).contiguous() for g in (g_w, g_lse, g_psum))
+        if ctx.fused:
+            from ..ops import device_ops
+            g = device_ops.moe_gate_backward(logits, lse, ids, ctx.renormalize, g_w, g_lse, g_psum)
+        else:
+            g = gate_backward_torch(logits, lse, ids, ctx.renormalize, g_w, g_lse, g_psum)
+        return g, None, None, None, None
+
+
+def route_topk(logits: torch.Tensor, top_k: int, renormalize: bool = False, ids_dtype=torch.int64,
+               stats: bool = False) -> GateResult:
+    """The router gate over ``logits`` [T, E], differentiable: softmax, the top K experts of every
+    token in the order (logit descending, expert index ascending; ``-inf`` is a mask), their
+    probabilities as gate weights (``renormalize``: divided by their sum), the row log-sum-exp and,
+    with ``stats``, ``prob_sum[e] = sum_t p[t, e]`` and ``counts[e]`` = tokens routed to e.
+
+    On a GPU tensor with ``E <= 2048`` and ``top_k <= 16`` forward and backward are the fused K10
+    kernels (one pass over the logits each, no host synchronisation, bit-reproducible); anywhere
+    else they are the same definition in torch."""
+    if logits.dim() != 2 or not logits.is_floating_point():
+        raise ValueError("route_topk: logits must be a floating-point [T, E] tensor")
+    if isinstance(top_k, bool) or not isinstance(top_k, int) or not 1 <= top_k <= logits.shape[1]:
+        raise ValueError(f"route_topk: top_k {top_k!r} is not an int in [1, E = {logits.shape[1]}]")
+    if ids_dtype not in (torch.int32, torch.int64):
+        raise ValueError("route_topk: ids_dtype must be int32 or int64")
+    return GateResult(*_RouteTopK.apply(logits, top_k, bool(renormalize), ids_dtype, bool(stats)))
+
+
 class ExpertParallelMoE(torch.nn.Module):
     """Top-k routed mixture of two-layer ReLU MLP experts, experts sharded over the ranks.
 
@@ -112,11 +231,26 @@ class ExpertParallelMoE(torch.nn.Module):
     assignments to every expert, its first in (token, k) order, in the padded layout of
     ``dispatchTokens(sourceCapacity=S)``: no host synchronisation in the step, and the local experts
     run as two batched GEMMs (``baddbmm`` over ``[local experts, p*S, d_model]``, ReLU between them)
-    instead of a ragged loop.  ``last_plan.kept`` / ``valid`` / ``dropped`` stay on the device."""
+    instead of a ragged loop.  ``last_plan.kept`` / ``valid`` / ``dropped`` stay on the device.
+
+    ``router="fused"`` routes through :func:`route_topk` (the K10 kernels on the GPU) instead of
+    :meth:`route`: a specified tie order, ``renormalize`` (gate weights divided by their sum over
+    the chosen K) and the router's auxiliary losses.  Every forward then stores ``last_aux_loss``,
+    over this rank's own tokens and with no collective, for the user to add to the loss:
+    ``aux_loss_coef * E * sum_e (counts[e] / (T*K)) * (prob_sum[e] / T) + z_loss_coef * mean_t
+    lse[t]^2``.  The default ``router="torch"`` is the layer as it was."""
 
     def __init__(self, comm, d_model: int, d_hidden: int, num_experts: int, top_k: int, seed: int = 0,
-                 device=None, dtype=torch.float32, operand=None, capacity_factor=None, source_capacity=None):
+                 device=None, dtype=torch.float32, operand=None, capacity_factor=None, source_capacity=None,
+                 router: str = "torch", renormalize: bool = False, aux_loss_coef: float = 0.0,
+                 z_loss_coef: float = 0.0):
         super().__init__()
+        if router not in ("torch", "fused"):
+            raise ValueError(f"router {router!r} is not 'torch' or 'fused'")
+        if router == "torch" and (renormalize or aux_loss_coef or z_loss_coef):
+            raise ValueError("renormalize, aux_loss_coef and z_loss_coef need router='fused'")
+        self.router_kind, self.renormalize = router, bool(renormalize)
+        self.aux_loss_coef, self.z_loss_coef, self.last_aux_loss = float(aux_loss_coef), float(z_loss_coef), None
         p, r = comm.getSlaveNum(), comm.getRank()
         if num_experts % p:
             raise ValueError(f"num_experts {num_experts} is not a multiple of the {p} ranks")
@@ -157,8 +291,20 @@ class ExpertParallelMoE(torch.nn.Module):
         probs = torch.softmax((x @ self.router).to(torch.float32), dim=-1)
         return torch.topk(probs, self.top_k, dim=-1)
 
+    def route_fused(self, x: torch.Tensor):
+        """:meth:`route` through :func:`route_topk`; stores ``last_aux_loss``."""
+        T, E, K = x.shape[0], self.num_experts, self.top_k
+        res = route_topk(x @ self.router, K, self.renormalize, stats=self.aux_loss_coef != 0.0)
+        aux = res.lse.new_zeros(())
+        if T and self.aux_loss_coef != 0.0:
+            aux = aux + self.aux_loss_coef * E * ((res.counts.to(torch.float32) / (T * K)) * (res.prob_sum / T)).sum()
+        if T and self.z_loss_coef != 0.0:
+            aux = aux + self.z_loss_coef * (res.lse * res.lse).mean()
+        self.last_aux_loss = aux
+        return res.weights, res.ids
+
     def forward(self, x: torch.Tensor) -> torch.Tensor:
-        w, ids = self.route(x)
+        w, ids = self.route_fused(x) if self.router_kind == "fused" else self.route(x)
         rows, plan = dispatch_tokens(self.comm, x, ids, self.num_experts, self.operand,
                                      capacity_factor=self.capacity_factor, source_capacity=self.source_capacity)
         self.last_plan = plan

@@ -646,6 +646,102 @@ def moe_combine_rows(rows: torch.Tensor, slots: torch.Tensor, weights: Optional[
     return out
 
 
+MOE_GATE_MAX_TOP_K = 16
+
+
+def _gate_shape(fn: str, logits: torch.Tensor, top_k) -> Tuple[int, int, int]:
+    """(T, E, K) of a K10 call, checked as csrc/kernels/moe_gate.hip checks them."""
+    if logits.dim() != 2 or logits.dtype not in MOE_DTYPES:
+        raise ValueError(f"{fn}: logits must be [T, E] in float32 / bfloat16 / float16")
+    T, E = int(logits.shape[0]), int(logits.shape[1])
+    if not 1 <= E <= MOE_MAX_EXPERTS:
+        raise ValueError(f"{fn}: E = {E} is not in [1, {MOE_MAX_EXPERTS}]")
+    if isinstance(top_k, bool) or not isinstance(top_k, int) or not 1 <= top_k <= min(E, MOE_GATE_MAX_TOP_K):
+        raise ValueError(f"{fn}: top_k {top_k!r} is not an int in [1, min(E, {MOE_GATE_MAX_TOP_K})]")
+    if T * top_k > (2 ** 31 - 1) // 2:
+        raise ValueError(f"{fn}: {T} tokens x top_k {top_k} is past the routed limit")
+    return T, E, top_k
+
+
+def moe_gate_topk(logits: torch.Tensor, top_k: int, renormalize: bool = False, ids_dtype=torch.int64,
+                  stats: bool = False, stream=None, out=None):
+    """K10's forward over ``logits`` [T, E]: ``(weights, ids, lse, prob_sum, counts)``.  ``ids``
+    [T, K] are the first K experts of a token in the order (logit descending, index ascending),
+    ``weights`` float32 [T, K] their softmax probabilities (divided by their sum with
+    ``renormalize``), ``lse`` float32 [T] the row's log-sum-exp.  With ``stats``: ``prob_sum``
+    float32 [E], the probabilities summed over the tokens in a fixed order, and ``counts`` int64 [E],
+    the tokens routed to every expert; both None without.  ``out``: the five tensors to write
+    (the last two None without ``stats``) instead of new ones.  Nothing is read back."""
+    fn = "moe_gate_topk"
+    _dev_check(logits)
+    T, E, K = _gate_shape(fn, logits, top_k)
+    if ids_dtype not in (torch.int32, torch.int64):
+        raise ValueError(f"{fn}: ids_dtype must be int32 or int64")
+    dev = logits.device
+    want = (((T, K), torch.float32), ((T, K), ids_dtype), ((T,), torch.float32), ((E,), torch.float32),
+            ((E,), torch.int64))[:5 if stats else 3]
+    if out is None:
+        out = tuple(torch.empty(shape, dtype=dt, device=dev) for shape, dt in want)
+    else:
+        out = tuple(out)
+        if len(out) != 5 or any(not isinstance(t, torch.Tensor) or tuple(t.shape) != shape or t.dtype != dt
+                                for t, (shape, dt) in zip(out, want)):
+            raise ValueError(f"{fn}: out must be (weights, ids, lse, prob_sum, counts) of the call's shapes and dtypes")
+        _dev_check(logits, *out)
+    weights, ids, lse = out[:3]
+    prob_sum, counts = out[3:] if stats else (None, None)
+    scratch = None
+    sb = 0
+    lib = native.hip()
+    dt = int(dtype_of_torch(logits.dtype))
+    if stats:
+        sb = lib.mp4x_moe_gate_scratch_bytes(dt, T, E)
+        scratch = torch.empty(max(sb, 1), dtype=torch.uint8, device=dev)
+    if T == 0 and not stats:
+        return weights, ids, lse, None, None
+    check(lib.mp4x_moe_gate_topk(dt, logits.data_ptr() if T else None, T, E, K, int(bool(renormalize)),
+                                 weights.data_ptr() if T else None, ids.data_ptr() if T else None,
+                                 int(ids_dtype == torch.int64), lse.data_ptr() if T else None,
+                                 prob_sum.data_ptr() if stats else None, counts.data_ptr() if stats else None,
+                                 scratch.data_ptr() if stats else None, sb, stream_ptr(stream)), "mp4x_moe_gate_topk")
+    return weights, ids, lse, prob_sum, counts
+
+
+def moe_gate_backward(logits: torch.Tensor, lse: torch.Tensor, ids: torch.Tensor, renormalize: bool = False,
+                      g_weights: Optional[torch.Tensor] = None, g_lse: Optional[torch.Tensor] = None,
+                      g_prob_sum: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None, stream=None):
+    """K10's backward: the gradient of ``logits`` (their dtype, one rounding) from the saved
+    ``logits``, ``lse`` and ``ids`` of :func:`moe_gate_topk` and the gradients of ``weights`` [T, K],
+    ``lse`` [T] and ``prob_sum`` [E], all float32, each None for zeros."""
+    fn = "moe_gate_backward"
+    _dev_check(logits, lse, ids, g_weights, g_lse, g_prob_sum, out)
+    if ids.dim() != 2 or ids.dtype not in (torch.int32, torch.int64):
+        raise ValueError(f"{fn}: ids must be [T, K] in int32 or int64")
+    T, E, K = _gate_shape(fn, logits, int(ids.shape[1]))
+    if ids.shape[0] != T:
+        raise ValueError(f"{fn}: {ids.shape[0]} rows of ids for {T} rows of logits")
+    for name, t, shape in (("lse", lse, (T,)), ("g_weights", g_weights, (T, K)), ("g_lse", g_lse, (T,)),
+                           ("g_prob_sum", g_prob_sum, (E,))):
+        if t is not None and (t.dtype != torch.float32 or tuple(t.shape) != shape):
+            raise ValueError(f"{fn}: {name} must be float32 {list(shape)}")
+    if lse is None:
+        raise ValueError(f"{fn}: lse is missing")
+    if out is None:
+        out = torch.empty_like(logits)
+    elif out.dtype != logits.dtype or out.shape != logits.shape:
+        raise ValueError(f"{fn}: out dtype / shape differ from the logits'")
+    if T == 0:
+        return out
+
+    def ptr(t):
+        return t.data_ptr() if t is not None else None
+    check(native.hip().mp4x_moe_gate_backward(int(dtype_of_torch(logits.dtype)), logits.data_ptr(), lse.data_ptr(),
+                                              ids.data_ptr(), int(ids.dtype == torch.int64), T, E, K,
+                                              int(bool(renormalize)), ptr(g_weights), ptr(g_lse), ptr(g_prob_sum),
+                                              out.data_ptr(), stream_ptr(stream)), "mp4x_moe_gate_backward")
+    return out
+
+
 # int64 key sorts: rocPRIM's own dispatch (block sort + merge passes below 1 M items, whatever the
 # key width) or forced onesweep (csrc/kernels/sparse.hip OnesweepSort: ~27 us per 8-bit pass at
 # 200 k items).  Measured on MI355X (profiles/r6/sparse/sort_ab.jsonl): onesweep wins at <= 16 bits
