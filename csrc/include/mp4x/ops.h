@@ -246,6 +246,33 @@ int mp4x_moe_gate_backward(int dtype, const void* logits, const float* lse, cons
                            int E, int K, int renormalize, const float* g_weights, const float* g_lse,
                            const float* g_prob_sum, void* g_logits, void* stream);
 
+// ---------------------------------------------------------------- K11 fused combine backward
+// Both gradients of mp4x_moe_combine from one pass over its output gradient g[T][width]: rows
+// [num_rows][width] are the rows the combine read (slot order), g_rows [num_rows][width] their
+// gradient; all three f32 / bf16 / f16 (else MP4X_E_UNSUPPORTED), rows of whole 16-byte vectors,
+// 16-byte aligned.  slots int64[T*K], weights and g_weights f32[T*K]; 1 <= K <= 16, 0 <= T <=
+// INT32_MAX / 2 / K, num_rows >= 1.  A null or misaligned pointer, a bad size, K > 16 and a g_rows
+// that overlaps rows or g are MP4X_E_BADARG before any launch; T == 0 launches nothing.
+// Per assignment a = t*K + k with s = slots[a] >= 0:
+//   g_rows[s]    = round_to_dtype(weights[a] * f32(g[t])): one multiply, one rounding, bit for bit
+//                  what mp4x_moe_route_scatter writes with row_scale;
+//   g_weights[a] = sum_h f32(g[t][h]) * f32(rows[s][h]) in f32 (contraction to FMA allowed), in an
+//                  order fixed by (dtype, width) alone;
+// with s < 0 no row is read or written and g_weights[a] = +0.0f.  Every slot value appears at most
+// once; a row of g_rows no slot names is not touched.  Deterministic: no atomics.
+int mp4x_moe_combine_backward(int dtype, const void* g, const void* rows, int64_t num_rows, const int64_t* slots,
+                              const float* weights, int64_t T, int K, int64_t width, void* g_rows, float* g_weights,
+                              void* stream);
+// The same into the padded layout after mp4x_moe_route_count / mp4x_moe_route_scatter_pad on the
+// same scratch (n = T*K assignments, nb experts, share cap; the slots are that scatter's): num_rows
+// = nb * cap, and the pad rows [min(cnt[e], cap), cap) of every expert block are then written as
+// all-zero bits by the fill kernel, so every row of g_rows is written exactly once, as
+// mp4x_moe_route_scatter_pad with row_scale leaves it.  n == 0 writes nb * cap zero rows and needs
+// neither g, rows, slots, weights, g_weights nor scratch.
+int mp4x_moe_combine_backward_pad(int dtype, const void* g, const void* rows, const int64_t* slots, const float* weights,
+                                  int64_t T, int K, int64_t width, int64_t n, int nb, int64_t cap, void* scratch,
+                                  size_t scratch_bytes, void* g_rows, float* g_weights, void* stream);
+
 // ---------------------------------------------------------------- errors
 // Reads and clears this thread's last HIP error.  mp4x reports its own failures through return
 // codes; a failed HIP call must not stay "last error" for PyTorch's next kernel-launch check to

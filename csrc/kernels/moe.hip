@@ -24,6 +24,9 @@
 //   combine        k_moe_combine  out[t] = sum over k, in k order, of w[t, k] * rows[slots[t, k]]:
 //                  a lane group per token reads its K rows through the slot index; the mul and
 //                  the add are separate roundings (no contraction), one rounding to the dtype
+//   combine bwd    k_moe_combine_bwd  (K11) both gradients of the combine from one pass over its output
+//                  gradient g: g_rows[slots[t, k]] = w[t, k] * g[t] (the scatter's bits with row_scale)
+//                  and g_w[t, k] = g[t] . rows[slots[t, k]] in f32, the same lane groups, no temporary
 //
 // The slot order is exactly the stable sort by expert id.  No global atomics anywhere: every
 // result is identical run to run.
@@ -264,6 +267,85 @@ __global__ __launch_bounds__(kBlock) void k_moe_combine(const u32x4* __restrict_
   }
 }
 
+// K11, the combine's backward in one pass over g: the lane groups of k_moe_combine.  A lane owns
+// the vectors sub, sub + G, ... of g[t]; per vector it loads g once, issues the loads of the (at
+// most kMoeBwdMaxK) live rows[slot] together, folds each into its slot's partial dot product (f32,
+// contraction allowed) and stores w * g (mul_rn: one multiply, one rounding) to g_rows[slot],
+// nontemporal.  The k loop has the fixed trip count kMoeBwdMaxK under the uniform guard k < K, so
+// slots, weights and partial sums sit in registers under compile-time indices (no scratch).  After
+// the row a __shfl_xor tree per k over the group, and lane 0 of the group writes g_weights: the
+// summation order is a function of (dtype, width) alone.  A slot < 0 reads and writes no row and
+// gives +0.0f.  No LDS, no atomics.  KMAX (4, 8 or 16, the smallest that holds K) only sizes those
+// registers: a small K keeps more waves resident; the arithmetic and its order do not depend on it.
+constexpr int kMoeBwdMaxK = 16;
+
+template <int DT, int KMAX>
+__global__ __launch_bounds__(kBlock) void k_moe_combine_bwd(const u32x4* __restrict__ g,
+                                                            const u32x4* __restrict__ rows,
+                                                            const int64_t* __restrict__ slots,
+                                                            const float* __restrict__ weights, int64_t T, int K,
+                                                            int64_t V, int G, int64_t nrows,
+                                                            u32x4* __restrict__ g_rows,
+                                                            float* __restrict__ g_weights) {
+  constexpr int W = 16 / sizeof(typename Elem<DT>::S);
+  const int lane = threadIdx.x & 63;
+  const int grp = lane / G, sub = lane % G, R = 64 / G;
+  const int64_t wave = wave_id();
+  const int64_t nwaves = ((int64_t)gridDim.x * kBlock) >> 6;
+  for (int64_t t = wave * R + grp; t < T; t += nwaves * R) {
+    const int64_t* sl = slots + t * K;
+    const float* wt = weights + t * K;
+    int64_t base[KMAX];            // slot * V, or -1
+    float wk[KMAX], dot[KMAX];
+#pragma unroll
+    for (int k = 0; k < KMAX; ++k) {
+      base[k] = -1;
+      wk[k] = 0.0f;
+      dot[k] = 0.0f;
+      if (k < K) {
+        const int64_t s = sl[k];
+        MP4X_DASSERT(s < nrows);
+        base[k] = s < 0 ? -1 : s * V;
+        wk[k] = wt[k];
+      }
+    }
+    for (int64_t v = sub; v < V; v += G) {
+      float a[W];
+      unpack<DT>(g[t * V + v], a);
+      u32x4 y[KMAX];
+#pragma unroll
+      for (int k = 0; k < KMAX; ++k)
+        if (k < K && base[k] >= 0) y[k] = rows[base[k] + v];
+#pragma unroll
+      for (int k = 0; k < KMAX; ++k) {
+        if (k < K && base[k] >= 0) {
+          float b[W];
+          unpack<DT>(y[k], b);
+#pragma unroll
+          for (int j = 0; j < W; ++j) dot[k] = __builtin_fmaf(a[j], b[j], dot[k]);
+        }
+      }
+#pragma unroll
+      for (int k = 0; k < KMAX; ++k) {
+        if (k < K && base[k] >= 0) {
+          float b[W];
+#pragma unroll
+          for (int j = 0; j < W; ++j) b[j] = mul_rn(wk[k], a[j]);
+          __builtin_nontemporal_store(pack<DT, u32x4>(b), g_rows + base[k] + v);
+        }
+      }
+    }
+#pragma unroll
+    for (int k = 0; k < KMAX; ++k) {
+      if (k < K) {
+        float d = dot[k];
+        for (int m = G >> 1; m > 0; m >>= 1) d += __shfl_xor(d, m);
+        if (sub == 0) g_weights[t * K + k] = d;
+      }
+    }
+  }
+}
+
 }  // namespace mp4x
 
 using namespace mp4x;
@@ -487,4 +569,72 @@ extern "C" int mp4x_moe_combine_rows(int dtype, const void* rows, int64_t num_ro
                                      const float* weights, int64_t T, int K, int64_t width, void* out, void* stream) {
   if (num_rows < 1) return MP4X_E_BADARG;
   return moe_combine_launch(dtype, rows, num_rows, slots, weights, T, K, width, out, stream);
+}
+
+namespace {
+bool moe_overlap(const void* a, int64_t a_bytes, const void* b, int64_t b_bytes) {
+  const uintptr_t pa = (uintptr_t)a, pb = (uintptr_t)b;
+  return pa < pb + (uintptr_t)b_bytes && pb < pa + (uintptr_t)a_bytes;
+}
+
+// Both K11 entry points: everything they refuse, then the launch (none when T == 0).
+int moe_combine_bwd_launch(int dtype, const void* g, const void* rows, int64_t num_rows, const int64_t* slots,
+                           const float* weights, int64_t T, int K, int64_t width, void* g_rows, float* g_weights,
+                           hipStream_t st) {
+  if (int e = moe_dtype_ok(dtype)) return e;
+  const int64_t row_bytes = width * elem_size(dtype);
+  if (T < 0 || K < 1 || K > kMoeBwdMaxK || width < 1 || (row_bytes & 15) || num_rows < 1) return MP4X_E_BADARG;
+  if (T == 0) return 0;
+  if (T > INT32_MAX / 2 / K || !g || !rows || !g_rows || (((uintptr_t)g | (uintptr_t)rows | (uintptr_t)g_rows) & 15) ||
+      !slots || ((uintptr_t)slots & 7) || !weights || ((uintptr_t)weights & 3) || !g_weights ||
+      ((uintptr_t)g_weights & 3))
+    return MP4X_E_BADARG;
+  if (moe_overlap(g_rows, num_rows * row_bytes, rows, num_rows * row_bytes) ||
+      moe_overlap(g_rows, num_rows * row_bytes, g, T * row_bytes))
+    return MP4X_E_BADARG;
+  const int64_t V = row_bytes / 16;
+  const int G = lane_group(V);
+  const int grid = grid_for((T * G + 63) / 64 * 64, 1);
+  return with_dtype(dtype, [&](auto dtc) {
+    constexpr int DT = decltype(dtc)::value;
+    if constexpr (DT == MP4X_F32 || DT == MP4X_BF16 || DT == MP4X_F16) {
+      auto launch = [&](auto kmax) {
+        hipLaunchKernelGGL((k_moe_combine_bwd<DT, decltype(kmax)::value>), dim3(grid), dim3(kBlock), 0, st,
+                           (const u32x4*)g, (const u32x4*)rows, slots, weights, T, K, V, G, num_rows, (u32x4*)g_rows,
+                           g_weights);
+        return (int)hipGetLastError();
+      };
+      return K <= 4 ? launch(IntC<4>{}) : (K <= 8 ? launch(IntC<8>{}) : launch(IntC<kMoeBwdMaxK>{}));
+    } else {
+      return (int)MP4X_E_UNSUPPORTED;
+    }
+  });
+}
+}  // namespace
+
+extern "C" int mp4x_moe_combine_backward(int dtype, const void* g, const void* rows, int64_t num_rows,
+                                         const int64_t* slots, const float* weights, int64_t T, int K, int64_t width,
+                                         void* g_rows, float* g_weights, void* stream) {
+  return moe_combine_bwd_launch(dtype, g, rows, num_rows, slots, weights, T, K, width, g_rows, g_weights,
+                                (hipStream_t)stream);
+}
+
+// K11 into the padded layout: the kernel writes the kept rows, the pad fill the rows [min(cnt[e],
+// cap), cap) of every expert block from the scan the plan's route left in scratch.
+extern "C" int mp4x_moe_combine_backward_pad(int dtype, const void* g, const void* rows, const int64_t* slots,
+                                             const float* weights, int64_t T, int K, int64_t width, int64_t n, int nb,
+                                             int64_t cap, void* scratch, size_t scratch_bytes, void* g_rows,
+                                             float* g_weights, void* stream) {
+  hipStream_t st = (hipStream_t)stream;
+  if (int e = moe_dtype_ok(dtype)) return e;
+  const int64_t row_bytes = width * elem_size(dtype);
+  if (nb < 1 || nb > kMoeMaxNb || cap < 1 || cap > INT32_MAX / nb || T < 0 || K < 1 || K > kMoeBwdMaxK ||
+      T > INT32_MAX / 2 / K || n != T * K || width < 1 || (row_bytes & 15) || !g_rows || ((uintptr_t)g_rows & 15))
+    return MP4X_E_BADARG;
+  if (n == 0) return moe_pad_fill_launch(nullptr, nb, cap, row_bytes / 16, g_rows, st);
+  if (!scratch || ((uintptr_t)scratch & 255) || scratch_bytes < mp4x_moe_route_scratch_bytes(n, nb)) return MP4X_E_BADARG;
+  if (int e = moe_combine_bwd_launch(dtype, g, rows, (int64_t)nb * cap, slots, weights, T, K, width, g_rows, g_weights, st))
+    return e;
+  const MoeScratch S = moe_scratch(scratch, scratch_bytes, n, nb);
+  return moe_pad_fill_launch(&S, nb, cap, row_bytes / 16, g_rows, st);
 }

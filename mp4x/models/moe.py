@@ -54,9 +54,9 @@ class _Dispatch(torch.autograd.Function):
 
 class _Combine(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, rows, weights, comm, plan, operand):
+    def forward(ctx, rows, weights, comm, plan, operand, backward="torch"):
         out, back = comm.combineTokens(rows.contiguous(), plan, weights, operand=operand, returnSlotRows=True)
-        ctx.comm, ctx.plan, ctx.operand = comm, plan, operand
+        ctx.comm, ctx.plan, ctx.operand, ctx.fused = comm, plan, operand, backward == "fused"
         ctx.save_for_backward(back, weights)
         return out
 
@@ -65,6 +65,9 @@ class _Combine(torch.autograd.Function):
         back, weights = ctx.saved_tensors
         plan = ctx.plan
         g = g.contiguous()
+        if ctx.fused and weights is not None:
+            g_rows, g_w = ctx.comm.combineTokensBackward(g, plan, weights, back, operand=ctx.operand)
+            return g_rows, (g_w if ctx.needs_input_grad[1] else None), None, None, None, None
         g_rows, _ = ctx.comm.device.dispatch_tokens(g, None, plan.num_experts, ctx.operand, plan=plan,
                                                     row_scale=weights)
         g_w = None
@@ -77,7 +80,7 @@ class _Combine(torch.autograd.Function):
                 g_w = torch.where(sl >= 0, g_w, torch.zeros_like(g_w)).view_as(weights)
             else:
                 g_w = torch.zeros_like(weights)
-        return g_rows, g_w, None, None, None
+        return g_rows, g_w, None, None, None, None
 
 
 def dispatch_tokens(comm, x: torch.Tensor, expert_ids: torch.Tensor, num_experts: int, operand=None, capacity=None,
@@ -89,9 +92,18 @@ def dispatch_tokens(comm, x: torch.Tensor, expert_ids: torch.Tensor, num_experts
     return _Dispatch.apply(x, comm, expert_ids, num_experts, operand, capacity, capacity_factor, source_capacity)
 
 
-def combine_tokens(comm, expert_rows: torch.Tensor, plan, weights: Optional[torch.Tensor] = None, operand=None):
-    """Differentiable ``comm.combineTokens`` (w.r.t. the rows and the weights)."""
-    return _Combine.apply(expert_rows, weights, comm, plan, operand)
+COMBINE_BACKWARDS = ("torch", "fused")
+
+
+def combine_tokens(comm, expert_rows: torch.Tensor, plan, weights: Optional[torch.Tensor] = None, operand=None,
+                   backward: str = "torch"):
+    """Differentiable ``comm.combineTokens`` (w.r.t. the rows and the weights).  ``backward="fused"``
+    takes both gradients from ``comm.combineTokensBackward`` when ``weights`` are given (the rows'
+    gradient has the same bits, the weights' is summed in another order); ``"torch"`` is the
+    dispatch with ``row_scale`` and the row dots in torch."""
+    if backward not in COMBINE_BACKWARDS:
+        raise ValueError(f"backward {backward!r} is not 'torch' or 'fused'")
+    return _Combine.apply(expert_rows, weights, comm, plan, operand, backward)
 
 
 # ---------------------------------------------------------------- the router gate (K10)
@@ -238,13 +250,21 @@ class ExpertParallelMoE(torch.nn.Module):
     the chosen K) and the router's auxiliary losses.  Every forward then stores ``last_aux_loss``,
     over this rank's own tokens and with no collective, for the user to add to the loss:
     ``aux_loss_coef * E * sum_e (counts[e] / (T*K)) * (prob_sum[e] / T) + z_loss_coef * mean_t
-    lse[t]^2``.  The default ``router="torch"`` is the layer as it was."""
+    lse[t]^2``.  The default ``router="torch"`` is the layer as it was.
+
+    ``combine_backward="fused"`` takes the combine's two gradients from one pass over the output
+    gradient (:func:`combine_tokens` with ``backward="fused"``, the K11 kernel on the GPU) instead of
+    a second dispatch and a ``[T, K, d_model]`` product in torch.  The default ``"torch"`` is the
+    layer as it was."""
 
     def __init__(self, comm, d_model: int, d_hidden: int, num_experts: int, top_k: int, seed: int = 0,
                  device=None, dtype=torch.float32, operand=None, capacity_factor=None, source_capacity=None,
                  router: str = "torch", renormalize: bool = False, aux_loss_coef: float = 0.0,
-                 z_loss_coef: float = 0.0):
+                 z_loss_coef: float = 0.0, combine_backward: str = "torch"):
         super().__init__()
+        if combine_backward not in COMBINE_BACKWARDS:
+            raise ValueError(f"combine_backward {combine_backward!r} is not 'torch' or 'fused'")
+        self.combine_backward = combine_backward
         if router not in ("torch", "fused"):
             raise ValueError(f"router {router!r} is not 'torch' or 'fused'")
         if router == "torch" and (renormalize or aux_loss_coef or z_loss_coef):
@@ -313,14 +333,14 @@ class ExpertParallelMoE(torch.nn.Module):
             # biases' and is never read back; its gradient row is zero)
             h = torch.relu(torch.baddbmm(self.b1.unsqueeze(1), rows, self.w1))
             y = torch.baddbmm(self.b2.unsqueeze(1), h, self.w2)
-            return combine_tokens(self.comm, y, plan, w.contiguous(), self.operand)
+            return combine_tokens(self.comm, y, plan, w.contiguous(), self.operand, self.combine_backward)
         outs, off = [], 0
         for e, c in enumerate(plan.expert_counts):
             h = torch.relu(rows[off:off + c] @ self.w1[e] + self.b1[e])
             outs.append(h @ self.w2[e] + self.b2[e])
             off += c
         y = torch.cat(outs) if outs else rows
-        return combine_tokens(self.comm, y, plan, w.contiguous(), self.operand)
+        return combine_tokens(self.comm, y, plan, w.contiguous(), self.operand, self.combine_backward)
 
     def sync_gradients(self) -> None:
         p = self.comm.getSlaveNum()

@@ -646,6 +646,76 @@ def moe_combine_rows(rows: torch.Tensor, slots: torch.Tensor, weights: Optional[
     return out
 
 
+MOE_COMBINE_BWD_MAX_TOP_K = 16       # csrc/kernels/moe.hip: kMoeBwdMaxK
+
+
+def moe_combine_backward(g: torch.Tensor, rows: torch.Tensor, slots: torch.Tensor, weights: torch.Tensor,
+                         num_tokens: int, top_k: int, out=None, pad=None, max_slot: Optional[int] = None, stream=None):
+    """K11, both gradients of :func:`moe_combine` in one pass over its output gradient ``g``
+    [T, ...]: ``(g_rows, g_weights)``.  ``rows`` are the rows the combine read (slot order).  Per
+    assignment ``a = t * top_k + k`` with ``s = slots[a] >= 0``: ``g_rows[s] = weights[a] * g[t]``
+    (one multiply, one rounding: the bits of :func:`moe_route_scatter` with ``row_scale``) and
+    ``g_weights[a] = sum_h g[t, h] * rows[s, h]`` in float32, in an order fixed by the dtype and the
+    row width; with ``s < 0`` no row is read or written and ``g_weights[a] = +0``.  Every slot value
+    appears at most once; a row of ``g_rows`` no slot names stays as it was.
+
+    ``out``: ``(g_rows, g_weights)`` to write instead of new tensors.  ``pad = (rc, cap)``, the
+    :class:`RouteCount` and the share of the :func:`moe_route_scatter_pad` that made ``slots``: the
+    padded layout, ``rc.nb * cap`` rows, where the pad rows of every expert block are written as
+    zeros as that scatter does (every row written exactly once) and nothing is read back.  Without
+    ``pad``, ``max_slot`` is the largest slot when the caller knows it (else it is read back)."""
+    fn = "moe_combine_backward"
+    _dev_check(g, rows, slots, weights)
+    width, _ = _moe_rows(fn, rows)
+    if isinstance(top_k, bool) or not isinstance(top_k, int) or not 1 <= top_k <= MOE_COMBINE_BWD_MAX_TOP_K:
+        raise ValueError(f"{fn}: top_k {top_k!r} is not an int in [1, {MOE_COMBINE_BWD_MAX_TOP_K}]")
+    n = num_tokens * top_k
+    if n > (2 ** 31 - 1) // 2:
+        raise ValueError(f"{fn}: {num_tokens} tokens x top_k {top_k} is past the routed limit")
+    if g.dtype != rows.dtype or tuple(g.shape) != (num_tokens,) + tuple(rows.shape[1:]):
+        raise ValueError(f"{fn}: g must be {(num_tokens,) + tuple(rows.shape[1:])} in the rows' dtype")
+    if slots.dtype != torch.int64 or slots.numel() != n:
+        raise ValueError(f"{fn}: slots must be int64, num_tokens * top_k of them")
+    if weights is None or weights.dtype != torch.float32 or weights.numel() != n:
+        raise ValueError(f"{fn}: weights must be float32, one per assignment")
+    if pad is not None:
+        rc, cap = pad
+        cap = _moe_share(fn, rc.nb, cap)
+        if rc.ids.numel() != n or rows.shape[0] != rc.nb * cap:
+            raise ValueError(f"{fn}: the padded layout has {rc.nb} x {cap} rows for {rc.ids.numel()} assignments")
+        _dev_check(g, rc.scratch)
+    if out is None:
+        out = (torch.empty_like(rows), torch.empty((num_tokens, top_k), dtype=torch.float32, device=g.device))
+    g_rows, g_weights = out
+    _dev_check(g, g_rows, g_weights)
+    if g_rows.dtype != rows.dtype or g_rows.shape != rows.shape:
+        raise ValueError(f"{fn}: out[0] dtype / shape differ from the rows'")
+    if g_weights.dtype != torch.float32 or g_weights.numel() != n:
+        raise ValueError(f"{fn}: out[1] must be float32, one per assignment")
+    lib, dt = native.hip(), int(dtype_of_torch(rows.dtype))
+    if pad is not None:
+        check(lib.mp4x_moe_combine_backward_pad(
+            dt, g.data_ptr() if n else None, rows.data_ptr(), slots.data_ptr() if n else None,
+            weights.data_ptr() if n else None, num_tokens, top_k, width, n, rc.nb, cap,
+            rc.scratch.data_ptr() if n else None, rc.scratch.numel() if n else 0, g_rows.data_ptr(),
+            g_weights.data_ptr() if n else None, stream_ptr(stream)), "mp4x_moe_combine_backward_pad")
+        return g_rows, g_weights
+    if n == 0:
+        return g_rows, g_weights
+    if max_slot is None:
+        max_slot = int(slots.max())
+    if max_slot >= rows.shape[0]:
+        raise ValueError(f"{fn}: slot {max_slot} past the {rows.shape[0]} rows")
+    src, dst = rows, g_rows
+    if rows.shape[0] == 0:                 # nothing is placed: the kernel still wants valid addresses
+        src = torch.zeros((2,) + tuple(rows.shape[1:]), dtype=rows.dtype, device=rows.device)
+        src, dst = src[:1], src[1:]
+    check(lib.mp4x_moe_combine_backward(dt, g.data_ptr(), src.data_ptr(), src.shape[0], slots.data_ptr(),
+                                        weights.data_ptr(), num_tokens, top_k, width, dst.data_ptr(),
+                                        g_weights.data_ptr(), stream_ptr(stream)), "mp4x_moe_combine_backward")
+    return g_rows, g_weights
+
+
 MOE_GATE_MAX_TOP_K = 16
 
 

@@ -1702,6 +1702,14 @@ class DeviceEngine(AutotuneMixin, ScheduleMixin, RootedMixin):
         self._count("moe.combine")
         return moe.combine(self, expert_rows, plan, weights, operand, return_slot_rows)
 
+    def combine_tokens_backward(self, g: torch.Tensor, plan, weights, slot_rows: torch.Tensor, operand=None):
+        """Both gradients of ``combine_tokens`` from its output gradient ``g``: the expert rows'
+        (``g`` dispatched again along the plan, rows scaled by the gate weights) and the weights'
+        (the row dots with ``slot_rows``), the local half in one fused pass (K11; parallel/moe.py)."""
+        from . import moe
+        self._count("moe.combine.backward")
+        return moe.combine_backward(self, g, plan, weights, slot_rows, operand)
+
     def reduce_map(self, mapData: Dict, operator, root: int):
         from .sparse import reduce_map_device
         self._count("reduce_map")
@@ -1801,6 +1809,7 @@ for _n in _TIER_ATTRS:
 _WATCHED = ["allreduce", "autotune_allreduce", "autotune_reduce_scatter", "autotune_allgather", "autotune_reduce",
             "autotune_broadcast", "autotune_gather", "autotune_scatter", "reduce_scatter", "allgather", "broadcast", "reduce", "gather",
             "scatter", "allreduce_map", "all_to_all_v", "reduce_map", "gather_map", "allgather_map",
-            "reduce_scatter_map", "scatter_map", "broadcast_map", "barrier", "dispatch_tokens", "combine_tokens"]
+            "reduce_scatter_map", "scatter_map", "broadcast_map", "barrier", "dispatch_tokens", "combine_tokens",
+            "combine_tokens_backward"]
 for _n in _WATCHED:
     setattr(DeviceEngine, _n, _watched(_n, getattr(DeviceEngine, _n)))

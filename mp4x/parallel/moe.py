@@ -48,7 +48,12 @@ count exchange, no host sync, and the pair can be recorded by ``DeviceEngine.cap
 A padded dispatch -> experts -> combine is, bit for bit, the uncapped call on the ids with every
 assignment past its per-(rank, expert) share replaced by -1 (``tests/moe_padded_ref.py``).
 
-GPU tensors run the K9 kernels (``csrc/kernels/moe.hip``); host tensors, and GPU tensors where
+The combine's backward (``combine_backward``, ``combineTokensBackward``) makes both of its gradients
+from the output gradient ``g``: the expert rows' is ``g`` dispatched again along the plan with the
+gate weights as row scale, the weights' the dot of ``g[t]`` with every slot row of token t.  Both
+walk the same slots of buffers of one shape, so one pass does both (K11) and the exchange follows.
+
+GPU tensors run the K9 / K11 kernels (``csrc/kernels/moe.hip``); host tensors, and GPU tensors where
 the native library is absent, run the torch implementation of the same contract below.
 """
 from __future__ import annotations
@@ -441,6 +446,65 @@ def combine(engine, expert_rows: torch.Tensor, plan: TokenPlan, weights=None, op
     back = return_rows(engine, expert_rows, plan, operand)
     out = combine_local(back, plan, weights)
     return (out, back) if return_slot_rows else out
+
+
+# ---------------------------------------------------------------- the combine's backward (K11)
+COMBINE_BWD_MAX_TOP_K = 16      # csrc/kernels/moe.hip: kMoeBwdMaxK; a larger K runs the torch form
+
+
+def _torch_combine_backward(g: torch.Tensor, plan: TokenPlan, weights: torch.Tensor, slot_rows: torch.Tensor):
+    """The torch form of K11's contract: (the gradient rows in slot order, g_weights float32 [T, K])."""
+    T, K = plan.num_tokens, plan.top_k
+    slots = plan.slots
+    if plan.source_capacity is not None:
+        send = _torch_pad_scatter(g, slots, K, weights, torch.empty_like(slot_rows))
+    else:
+        a = torch.nonzero(slots >= 0).reshape(-1)
+        order = torch.empty_like(a)
+        order[slots[a]] = a                  # the placed assignments in slot order
+        send = _torch_scatter(g, order, K, weights)
+    sl = slots.view(T, K)
+    if slot_rows.shape[0] and T:
+        y = slot_rows.reshape(slot_rows.shape[0], -1)[sl.clamp(min=0)].to(torch.float32)      # [T, K, H]
+        g_w = (g.reshape(T, 1, -1).to(torch.float32) * y).sum(-1)
+        g_w = torch.where(sl >= 0, g_w, torch.zeros_like(g_w))
+    else:
+        g_w = torch.zeros((T, K), dtype=torch.float32, device=g.device)
+    return send, g_w
+
+
+def combine_backward(engine, g: torch.Tensor, plan: TokenPlan, weights: torch.Tensor, slot_rows: torch.Tensor,
+                     operand=None):
+    """``(g_expert_rows, g_weights)``: see ``ProcessCommSlave.combineTokensBackward``."""
+    what = "combineTokensBackward"
+    if not isinstance(plan, TokenPlan):
+        raise Mp4jException(f"{what}: plan must be the TokenPlan dispatchTokens returned")
+    padded = plan.source_capacity is not None
+    _check_rows(what, g, padded=padded)
+    _check_plan_rows(what, g, plan, plan.num_tokens)
+    if weights is None:
+        raise Mp4jException(f"{what}: weights are needed (without them the backward is dispatchTokens along the plan)")
+    weights = _check_weights(weights, plan, g)
+    nrows = plan.num_experts * plan.source_capacity if padded else sum(plan.send_counts)
+    if not isinstance(slot_rows, torch.Tensor) or slot_rows.dim() < 1 or not slot_rows.is_contiguous():
+        raise Mp4jException(f"{what}: slotRows must be the contiguous rows combineTokens(returnSlotRows=True) returned")
+    _check_plan_rows(f"{what}: slotRows", slot_rows, plan, nrows)
+    T, K = plan.num_tokens, plan.top_k
+    if _native_ok(g) and K <= COMBINE_BWD_MAX_TOP_K:
+        from ..ops.device_ops import moe_combine_backward
+        if padded:
+            send, _, _ = _pad_buffers(g, plan.num_experts, plan.source_capacity, len(plan.matrix), counts=False)
+            _, g_w = moe_combine_backward(g, slot_rows, plan.slots, weights, T, K, pad=(plan._route, plan.source_capacity),
+                                          out=(send, torch.empty((T, K), dtype=torch.float32, device=g.device)))
+        else:
+            send, g_w = moe_combine_backward(g, slot_rows, plan.slots, weights, T, K, max_slot=nrows - 1)
+    else:
+        send, g_w = _torch_combine_backward(g, plan, weights, slot_rows)
+    g_w = g_w.view_as(weights)
+    if padded:
+        got, _ = _pad_exchange(engine, send, None, None, operand)
+        return _pad_regroup(got, plan, inverse=False), g_w
+    return _forward_rows(engine, send, plan, operand), g_w
 
 
 # ---------------------------------------------------------------- the padded fixed-capacity layout

@@ -1042,6 +1042,27 @@ class ProcessCommSlave:
             raise Mp4jException("combineTokens needs a torch tensor (device engine)")
         return self.device.combine_tokens(expertRows, plan, weights, operand, returnSlotRows)
 
+    def combineTokensBackward(self, grad, plan, weights, slotRows, operand: Optional[Operand] = None):
+        """Both gradients of :meth:`combineTokens` (extension): ``(gExpertRows, gWeights)`` from the
+        gradient ``grad`` ``[T, ...]`` of its output, its ``weights`` ``[T, K]`` float32 and the
+        ``slotRows`` it returned with ``returnSlotRows=True``.
+
+        ``gExpertRows`` has the layout of ``expertRows`` and is, bit for bit, ``grad`` dispatched
+        again along the plan with every assignment's row times its weight (one multiply, one
+        rounding).  ``gWeights[t, k]`` is the float32 dot product of ``grad[t]`` with the slot row
+        of assignment (t, k), within ``(width + 2) * 2^-24 * sum |grad * row|`` of the exact value,
+        and +0 for a clipped or dropped assignment.  On GPU tensors with ``K <= 16`` both come from
+        one fused pass over ``grad`` (K11) with no temporary; the exchange is the plan's (no count
+        exchange, and along a padded plan no host synchronisation).  A collective: every rank calls it.
+
+        Raises :class:`Mp4jException` for weights that are absent or not float32 ``[T, K]``, a
+        ``grad`` that does not match the plan's tokens, and ``slotRows`` that are not the plan's
+        slot-order buffer (``sum(plan.send_counts)`` rows, ``E * S`` along a padded plan)."""
+        self._tick("combineTokensBackward")
+        if not _is_torch(grad):
+            raise Mp4jException("combineTokensBackward needs a torch tensor (device engine)")
+        return self.device.combine_tokens_backward(grad, plan, weights, slotRows, operand)
+
     # ================================================================ allreduce
     def allreduceArray(self, arrData, operand: Operand, operator, frm: int, to: int, out=None, scale: float = 1.0):
         """reduce-scatter + allgather with the last rank taking the remainder (reference :1733-1763).
