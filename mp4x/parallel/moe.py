@@ -111,6 +111,18 @@ class TokenPlan:
     def num_rows(self) -> int:
         return sum(self.expert_counts)
 
+    def segment_table(self):
+        """The rows of every local expert as the table :func:`grouped_mm_torch` takes.  A
+        padded plan: ``("padded", valid, S)``, the plan's own ``valid`` (rewritten by every replay of
+        a captured dispatch).  A ragged plan: ``("ragged", offsets)``, int64 ``[E/p + 1]`` on the
+        slots' device, the running sum of ``expert_counts``."""
+        if self.source_capacity is not None:
+            return ("padded", self.valid, self.source_capacity)
+        offsets = [0]
+        for c in self.expert_counts:
+            offsets.append(offsets[-1] + int(c))
+        return ("ragged", torch.tensor(offsets, dtype=torch.int64).to(self.slots.device))
+
 
 def _native_ok(t: torch.Tensor) -> bool:
     if not t.is_cuda:
@@ -505,6 +517,86 @@ def combine_backward(engine, g: torch.Tensor, plan: TokenPlan, weights: torch.Te
         got, _ = _pad_exchange(engine, send, None, None, operand)
         return _pad_regroup(got, plan, inverse=False), g_w
     return _forward_rows(engine, send, plan, operand), g_w
+
+
+# ---------------------------------------------------------------- the grouped expert GEMM: its definition
+GROUPED_MM_ACTS = (None, "relu")
+
+
+def _table_segments(table, rows: torch.Tensor, G: int) -> List[List[Tuple[int, int]]]:
+    """Per group the ``(first row, row count)`` segments it owns in ``rows`` flattened to
+    ``[R, width]``; reads the table on the host (the torch form only)."""
+    if not isinstance(table, tuple) or not table or table[0] not in ("ragged", "padded"):
+        raise ValueError("segment table must be ('ragged', offsets) or ('padded', valid, S)")
+    if table[0] == "ragged":
+        if len(table) != 2 or rows.dim() != 2 or table[1].numel() != G + 1:
+            raise ValueError(f"a ragged table is ('ragged', offsets [{G + 1}]) over rows [R, width]")
+        R, prev, segs = rows.shape[0], 0, []
+        for hi in table[1].tolist()[1:]:
+            hi = max(prev, min(int(hi), R))
+            segs.append([(prev, hi - prev)])
+            prev = hi
+        return segs
+    if len(table) != 3 or table[1].dim() != 2 or table[1].shape[0] != G:
+        raise ValueError(f"a padded table is ('padded', valid [{G}, B], S)")
+    B, S = table[1].shape[1], table[2]
+    if isinstance(S, bool) or not isinstance(S, int) or S < 1 or B < 1:
+        raise ValueError(f"a padded table's share S {S!r} must be an int >= 1 and B >= 1")
+    if rows.dim() != 3 or tuple(rows.shape[:2]) != (G, B * S):
+        raise ValueError(f"rows along this padded table are [{G}, {B * S}, width], not {tuple(rows.shape)}")
+    valid = table[1].tolist()
+    return [[((g * B + b) * S, max(0, min(int(valid[g][b]), S))) for b in range(B)] for g in range(G)]
+
+
+def grouped_mm_torch(x: torch.Tensor, w: torch.Tensor, table, bias: Optional[torch.Tensor] = None, act=None,
+                     transpose_w: bool = False, mask: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The definition of the grouped GEMM in torch (float32 on the exactly converted operands, one
+    rounding): ``out[r] = act(x[r] @ W[g] + bias[g])`` for the rows r group g owns along ``table``,
+    +0 where ``mask <= 0``, and +0 in every row nobody owns (those rows of ``x`` and ``mask`` are
+    never read).  It reads the table on the host; a kernel for it must not."""
+    if act not in GROUPED_MM_ACTS:
+        raise ValueError(f"act {act!r} is not None or 'relu'")
+    G = w.shape[0]
+    N = w.shape[1] if transpose_w else w.shape[2]
+    segs = _table_segments(table, x, G)
+    xf = x.reshape(-1, x.shape[-1])
+    out = torch.zeros((xf.shape[0], N), dtype=x.dtype, device=x.device)
+    mf = None if mask is None else mask.reshape(-1, N)
+    for g in range(G):
+        wg = w[g].to(torch.float32)
+        wg = wg.t() if transpose_w else wg
+        for lo, n in segs[g]:
+            if n == 0:
+                continue
+            v = xf[lo:lo + n].to(torch.float32) @ wg
+            if bias is not None:
+                v = v + bias[g].to(torch.float32)
+            if act == "relu":
+                v = torch.relu(v)
+            if mf is not None:
+                v = torch.where(mf[lo:lo + n].to(torch.float32) <= 0, torch.zeros_like(v), v)
+            out[lo:lo + n] = v.to(x.dtype)
+    return out.view(tuple(x.shape[:-1]) + (N,))
+
+
+def grouped_mm_wgrad_torch(x: torch.Tensor, gy: torch.Tensor, table, want_bias: bool = True):
+    """The definition of the grouped weight gradient in torch: ``(gw [G, Kd, N], gb [G, N] or None)``,
+    ``gw[g] = sum_r x[r]^T gy[r]`` and ``gb[g] = sum_r gy[r]`` over the rows group g owns, float32 on
+    the exactly converted operands, one rounding; +0 for a group without rows."""
+    G = table[1].shape[0] - 1 if table[0] == "ragged" else table[1].shape[0]
+    segs = _table_segments(table, x, G)
+    Kd, N = x.shape[-1], gy.shape[-1]
+    xf, gf = x.reshape(-1, Kd), gy.reshape(-1, N)
+    gw = torch.zeros((G, Kd, N), dtype=torch.float32, device=x.device)
+    gb = torch.zeros((G, N), dtype=torch.float32, device=x.device)
+    for g in range(G):
+        for lo, n in segs[g]:
+            if n == 0:
+                continue
+            xs, gs = xf[lo:lo + n].to(torch.float32), gf[lo:lo + n].to(torch.float32)
+            gw[g] += xs.t() @ gs
+            gb[g] += gs.sum(0)
+    return gw.to(x.dtype), (gb.to(x.dtype) if want_bias else None)
 
 
 # ---------------------------------------------------------------- the padded fixed-capacity layout
