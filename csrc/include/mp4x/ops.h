@@ -246,6 +246,42 @@ int mp4x_moe_gate_backward(int dtype, const void* logits, const float* lse, cons
                            int E, int K, int renormalize, const float* g_weights, const float* g_lse,
                            const float* g_prob_sum, void* g_logits, void* stream);
 
+// ---------------------------------------------------------------- K13 group-limited router gate
+// K10's gate with a choice of score, a selection bias, group-limited selection and a scaling factor.
+// logits, T, E, K, weights, ids, prob_sum, counts, scratch and their refusals are K10's.  score: 0 =
+// softmax (s = K10's p; lse is written and must not be NULL), 1 = sigmoid (s_j = 1 / (1 + exp(-l_j));
+// lse is not touched and may be NULL); any other value is MP4X_E_UNSUPPORTED.  bias: f32[E] or NULL.
+// 1 <= n_group <= 32 with E % n_group == 0 (groups of n = E / n_group contiguous columns), 1 <=
+// topk_group <= n_group, K <= topk_group * n, scale finite and > 0, else MP4X_E_BADARG; bias,
+// group_ids and lse are 4-byte aligned.  Every refusal comes before any launch.
+// Selection score c_j = s_j + bias[j] (one rounding; s_j without a bias), -inf where l_j = -inf.  A
+// group's score is the sum (one f32 addition) of its two largest c, or its largest alone when the
+// second is -inf.  The chosen groups are the first topk_group in (score descending, group ascending)
+// and go to group_ids[t][0 .. topk_group) (int32, optional) in that order.  ids[t][k] are the first K
+// columns of the chosen groups in (key descending, column ascending): the key is the logit in K10's
+// order without a bias, c with one.  For any bits the ids are distinct, inside [0, E) and inside the
+// chosen groups, which are distinct and inside [0, n_group).  weights[t][k] = s[ids[t][k]], divided
+// by their sum in k order when renormalize != 0, then multiplied by scale.  prob_sum[e] = sum_t
+// s[t][e] and counts[e] in K10's fixed order.  T == 0 launches nothing, or with the statistics writes
+// their zeros.
+size_t mp4x_moe_gate_group_scratch_bytes(int dtype, int64_t T, int E);
+int mp4x_moe_gate_group_topk(int dtype, const void* logits, const float* bias, int64_t T, int E, int K, int n_group,
+                             int topk_group, int score, int renormalize, float scale, float* weights, void* ids,
+                             int ids_are_i64, int32_t* group_ids, float* lse, float* prob_sum, int64_t* counts,
+                             void* scratch, size_t scratch_bytes, void* stream);
+// Backward from the saved logits, ids and (softmax) lse; the bias has no gradient.  With q_k the
+// score of column ids[t][k] and S their sum in k order:
+//   gq_k = scale * g_weights[t][k], or scale * ((g_weights[t][k] - sum_i g_weights[t][i] * (q_i / S)) / S)
+//   when renormalize;  gp_j = g_prob_sum[j] + sum_k [ids[t][k] == j] gq_k;
+//   softmax: g_logits[t][j] = round_to_dtype(p_j * (gp_j - sum_i gp_i p_i) + g_lse[t] * p_j), p_j = exp(l_j - lse[t]);
+//   sigmoid: g_logits[t][j] = round_to_dtype(d_j * gp_j), d_j = sigmoid(l_j) * sigmoid(-l_j), each factor
+//   by the forward's formula; lse and g_lse are not read.
+// NULL gradients are zeros; an id outside [0, E) takes no part (never an address).  T == 0 is 0.
+int mp4x_moe_gate_group_backward(int dtype, const void* logits, const float* lse, const void* ids, int ids_are_i64,
+                                 int64_t T, int E, int K, int score, int renormalize, float scale,
+                                 const float* g_weights, const float* g_lse, const float* g_prob_sum, void* g_logits,
+                                 void* stream);
+
 // ---------------------------------------------------------------- K11 fused combine backward
 // Both gradients of mp4x_moe_combine from one pass over its output gradient g[T][width]: rows
 // [num_rows][width] are the rows the combine read (slot order), g_rows [num_rows][width] their

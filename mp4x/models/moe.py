@@ -225,6 +225,183 @@ def route_topk(logits: torch.Tensor, top_k: int, renormalize: bool = False, ids_
     return GateResult(*_RouteTopK.apply(logits, top_k, bool(renormalize), ids_dtype, bool(stats)))
 
 
+# ---------------------------------------------------------------- the group-limited router gate (K13)
+GATE_MAX_GROUPS = 32                              # csrc/kernels/moe_gate_group.hip: kGateMaxGroups
+GATE_SCORES = ("softmax", "sigmoid")
+
+
+class GroupedGateResult(NamedTuple):
+    """What :func:`route_topk_grouped` returns.  ``weights`` float32 [T, K], ``lse`` float32 [T]
+    (None for the sigmoid score) and ``prob_sum`` float32 [E] are differentiable; ``ids`` [T, K],
+    ``counts`` int64 [E] and ``group_ids`` int32 [T, topk_group] are not.  ``prob_sum`` and
+    ``counts`` are None without ``stats``."""
+    weights: torch.Tensor
+    ids: torch.Tensor
+    lse: Optional[torch.Tensor]
+    prob_sum: Optional[torch.Tensor]
+    counts: Optional[torch.Tensor]
+    group_ids: torch.Tensor
+
+
+def _sigmoid(x: torch.Tensor) -> torch.Tensor:
+    return 1.0 / (1.0 + torch.exp(-x))
+
+
+def gate_group_forward_torch(logits: torch.Tensor, top_k: int, score: str, bias: Optional[torch.Tensor], n_group: int,
+                             topk_group: int, renormalize: bool, scale: float, ids_dtype, stats: bool):
+    """The definition of the group-limited gate in torch (float32 on the exactly converted logits):
+    what K13 computes, for host tensors and for shapes outside the kernel's range.
+    ``(weights, ids, lse, prob_sum, counts, group_ids)``."""
+    lg = logits.to(torch.float32)
+    T, E = lg.shape
+    n = E // n_group
+    lse = None
+    if score == "softmax":
+        m = lg.max(dim=-1, keepdim=True).values if T else lg.new_zeros((0, 1))
+        ex = torch.exp(lg - m)
+        total = ex.sum(dim=-1, keepdim=True)
+        lse = (m + torch.log(total)).squeeze(-1)
+        s = ex / total
+    else:
+        s = _sigmoid(lg)
+    neg = torch.full_like(s, float("-inf"))
+    c = torch.where(lg == float("-inf"), neg, s if bias is None else s + bias.to(torch.float32))
+    # a group's score: its two largest selection scores in one addition, the largest alone when the
+    # second is -inf (one live column, or a group of one)
+    top = c.view(T, n_group, n).topk(min(2, n), dim=-1).values
+    gs = top[..., 0]
+    if n > 1:
+        gs = torch.where(top[..., 1] == float("-inf"), top[..., 0], top[..., 0] + top[..., 1])
+    # (group score descending, group index ascending): the stable sort keeps equal scores in index order
+    group_ids = torch.sort(gs, dim=-1, descending=True, stable=True).indices[:, :topk_group]
+    inside = torch.zeros(T, n_group, dtype=torch.bool, device=lg.device).scatter_(1, group_ids, True)
+    inside = inside.repeat_interleave(n, dim=1)
+    # (key descending, index ascending) over the columns of the chosen groups: the key is the logit
+    # without a bias, the selection score with one; a second stable sort moves the other groups' columns behind
+    order = torch.sort(lg if bias is None else c, dim=-1, descending=True, stable=True).indices
+    keep = torch.sort(inside.gather(1, order).to(torch.int8), dim=-1, descending=True, stable=True).indices
+    ids = order.gather(1, keep)[:, :top_k]
+    w = s.gather(1, ids)
+    if renormalize:
+        w = w / _sum_in_k_order(w).unsqueeze(1)
+    w = w * scale
+    prob_sum = counts = None
+    if stats:
+        prob_sum = s.sum(dim=0)
+        counts = torch.bincount(ids.reshape(-1), minlength=E)
+    return w, ids.to(ids_dtype), lse, prob_sum, counts, group_ids.to(torch.int32)
+
+
+def gate_group_backward_torch(logits: torch.Tensor, lse: Optional[torch.Tensor], ids: torch.Tensor, score: str,
+                              renormalize: bool, scale: float, g_weights: Optional[torch.Tensor],
+                              g_lse: Optional[torch.Tensor], g_prob_sum: Optional[torch.Tensor]) -> torch.Tensor:
+    """The closed-form backward of the group-limited gate in torch, from the saved logits, ids and
+    (softmax) lse; an absent gradient counts as zero; the bias has no gradient.  One rounding to the
+    logits' dtype."""
+    lg = logits.to(torch.float32)
+    ids = ids.to(torch.int64)
+    p = torch.exp(lg - lse.unsqueeze(1)) if score == "softmax" else _sigmoid(lg)
+    gp = torch.zeros_like(p) if g_prob_sum is None else g_prob_sum.unsqueeze(0).expand_as(p).clone()
+    if g_weights is not None:
+        gq = g_weights
+        if renormalize:
+            q = p.gather(1, ids)
+            s = _sum_in_k_order(q).unsqueeze(1)
+            gq = (g_weights - _sum_in_k_order(g_weights * (q / s)).unsqueeze(1)) / s
+        gp.scatter_add_(1, ids, gq * scale)
+    if score == "softmax":
+        dot = (gp * p).sum(dim=-1, keepdim=True)
+        g = p * (gp - dot)
+        if g_lse is not None:
+            g = g + g_lse.unsqueeze(1) * p
+    else:
+        g = (p * _sigmoid(-lg)) * gp              # sigmoid(l) * sigmoid(-l): never 1 - s
+    return g.to(logits.dtype)
+
+
+def _gate_group_is_fused(logits: torch.Tensor, top_k: int, n_group: int) -> bool:
+    return _gate_is_fused(logits, top_k) and n_group <= GATE_MAX_GROUPS
+
+
+class _RouteTopKGrouped(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, logits, bias, top_k, score, n_group, topk_group, renormalize, scale, ids_dtype, stats):
+        logits = logits.contiguous()
+        ctx.fused = _gate_group_is_fused(logits, top_k, n_group)
+        if ctx.fused:
+            from ..ops import device_ops
+            w, ids, lse, prob_sum, counts, group_ids = device_ops.moe_gate_group_topk(
+                logits, top_k, score, bias, n_group, topk_group, renormalize, scale, ids_dtype, stats)
+        else:
+            w, ids, lse, prob_sum, counts, group_ids = gate_group_forward_torch(
+                logits, top_k, score, bias, n_group, topk_group, renormalize, scale, ids_dtype, stats)
+        ctx.score, ctx.renormalize, ctx.scale = score, renormalize, scale
+        ctx.save_for_backward(logits, lse, ids)
+        ctx.set_materialize_grads(False)
+        ctx.mark_non_differentiable(*(t for t in (ids, counts, group_ids) if t is not None))
+        return w, ids, lse, prob_sum, counts, group_ids
+
+    @staticmethod
+    def backward(ctx, g_w, _g_ids, g_lse, g_psum, _g_counts, _g_groups):
+        logits, lse, ids = ctx.saved_tensors
+        g_w, g_lse, g_psum = (None if g is None else g.to(torch.float32).contiguous() for g in (g_w, g_lse, g_psum))
+        if ctx.fused:
+            from ..ops import device_ops
+            g = device_ops.moe_gate_group_backward(logits, lse, ids, ctx.score, ctx.renormalize, ctx.scale, g_w, g_lse,
+                                                   g_psum)
+        else:
+            g = gate_group_backward_torch(logits, lse, ids, ctx.score, ctx.renormalize, ctx.scale, g_w, g_lse, g_psum)
+        return (g,) + (None,) * 9
+
+
+def route_topk_grouped(logits: torch.Tensor, top_k: int, *, score: str = "sigmoid", bias: Optional[torch.Tensor] = None,
+                       n_group: int = 1, topk_group: Optional[int] = None, renormalize: bool = False, scale: float = 1.0,
+                       ids_dtype=torch.int64, stats: bool = False) -> GroupedGateResult:
+    """The group-limited, bias-corrected router gate over ``logits`` [T, E], differentiable in the
+    logits (the bias steers the selection only and has no gradient).
+
+    The score s is the softmax over the experts or ``1 / (1 + exp(-l))``.  The selection score is
+    ``s + bias`` (``bias`` float32 [E]; ``-inf`` logits are a mask).  The E experts form ``n_group``
+    contiguous groups; a token takes the ``topk_group`` groups with the largest sum of their two
+    largest selection scores (ties to the smaller group index; ``group_ids``), then the first K
+    experts inside them in the order (selection score descending, expert index ascending; without a
+    bias the logits' own order, which is :func:`route_topk`'s for any bits).  The gate weights are
+    the chosen s, with ``renormalize`` divided by their sum, times ``scale``.  ``lse`` exists for the
+    softmax score only.  With ``stats``: ``prob_sum[e] = sum_t s[t, e]`` and ``counts[e]``.
+
+    On a GPU tensor with ``E <= 2048``, ``top_k <= 16`` and ``n_group <= 32`` forward and backward are
+    the fused K13 kernels (no host synchronisation, bit-reproducible); anywhere else they are the
+    same definition in torch."""
+    fn = "route_topk_grouped"
+    if logits.dim() != 2 or not logits.is_floating_point():
+        raise ValueError(f"{fn}: logits must be a floating-point [T, E] tensor")
+    E = logits.shape[1]
+    if isinstance(top_k, bool) or not isinstance(top_k, int) or not 1 <= top_k <= E:
+        raise ValueError(f"{fn}: top_k {top_k!r} is not an int in [1, E = {E}]")
+    if score not in GATE_SCORES:
+        raise ValueError(f"{fn}: score {score!r} is not 'softmax' or 'sigmoid'")
+    if isinstance(n_group, bool) or not isinstance(n_group, int) or n_group < 1 or E % n_group:
+        raise ValueError(f"{fn}: n_group {n_group!r} is not a positive int that divides E = {E}")
+    if topk_group is None:
+        topk_group = n_group
+    if isinstance(topk_group, bool) or not isinstance(topk_group, int) or not 1 <= topk_group <= n_group:
+        raise ValueError(f"{fn}: topk_group {topk_group!r} is not an int in [1, n_group = {n_group}]")
+    if top_k > topk_group * (E // n_group):
+        raise ValueError(f"{fn}: top_k {top_k} is more than the {topk_group} x {E // n_group} experts of the chosen groups")
+    if bias is not None:
+        if (not isinstance(bias, torch.Tensor) or bias.dtype != torch.float32 or tuple(bias.shape) != (E,)
+                or bias.device != logits.device):
+            raise ValueError(f"{fn}: bias must be a float32 [{E}] tensor on the logits' device")
+        bias = bias.detach().contiguous()
+    scale = float(scale)
+    if not (scale > 0.0 and scale != float("inf")):
+        raise ValueError(f"{fn}: scale {scale!r} is not finite and positive")
+    if ids_dtype not in (torch.int32, torch.int64):
+        raise ValueError(f"{fn}: ids_dtype must be int32 or int64")
+    return GroupedGateResult(*_RouteTopKGrouped.apply(logits, bias, top_k, score, n_group, topk_group, bool(renormalize),
+                                                      scale, ids_dtype, bool(stats)))
+
+
 class ExpertParallelMoE(torch.nn.Module):
     """Top-k routed mixture of two-layer ReLU MLP experts, experts sharded over the ranks.
 
@@ -252,6 +429,19 @@ class ExpertParallelMoE(torch.nn.Module):
     ``aux_loss_coef * E * sum_e (counts[e] / (T*K)) * (prob_sum[e] / T) + z_loss_coef * mean_t
     lse[t]^2``.  The default ``router="torch"`` is the layer as it was.
 
+    ``score``, ``expert_groups``, ``topk_groups``, ``routed_scale`` and ``balance_bias`` (all need
+    ``router="fused"``) route through :func:`route_topk_grouped` (the K13 kernels on the GPU):
+    ``score="sigmoid"`` scores every expert on its own (no ``lse``: ``z_loss_coef`` is refused);
+    ``expert_groups=Gr`` splits the experts into Gr contiguous groups of which a token uses
+    ``topk_groups``; ``routed_scale`` multiplies the gate weights.  With this layer's contiguous
+    expert sharding ``expert_groups=p`` makes a group a rank, so a token's rows then reach at most
+    ``topk_groups`` ranks.  ``balance_bias`` holds a replicated float32 buffer ``expert_bias`` [E]
+    (in ``state_dict``, not a Parameter) that is added to the scores for the selection only, keeps
+    the last forward's ``counts`` in ``last_counts`` (``last_ids`` and ``last_group_ids`` are the
+    last forward's choices), and :meth:`update_balance_bias` moves the bias
+    against the load.  The auxiliary loss keeps its formula with ``prob_sum = sum_t s``.  With none
+    of these given the layer is what it was, with both routers.
+
     ``combine_backward="fused"`` takes the combine's two gradients from one pass over the output
     gradient (:func:`combine_tokens` with ``backward="fused"``, the K11 kernel on the GPU) instead of
     a second dispatch and a ``[T, K, d_model]`` product in torch.  The default ``"torch"`` is the
@@ -260,7 +450,9 @@ class ExpertParallelMoE(torch.nn.Module):
     def __init__(self, comm, d_model: int, d_hidden: int, num_experts: int, top_k: int, seed: int = 0,
                  device=None, dtype=torch.float32, operand=None, capacity_factor=None, source_capacity=None,
                  router: str = "torch", renormalize: bool = False, aux_loss_coef: float = 0.0,
-                 z_loss_coef: float = 0.0, combine_backward: str = "torch"):
+                 z_loss_coef: float = 0.0, combine_backward: str = "torch", score: str = "softmax",
+                 expert_groups: Optional[int] = None, topk_groups: Optional[int] = None, routed_scale: float = 1.0,
+                 balance_bias: bool = False):
         super().__init__()
         if combine_backward not in COMBINE_BACKWARDS:
             raise ValueError(f"combine_backward {combine_backward!r} is not 'torch' or 'fused'")
@@ -271,12 +463,37 @@ class ExpertParallelMoE(torch.nn.Module):
             raise ValueError("renormalize, aux_loss_coef and z_loss_coef need router='fused'")
         self.router_kind, self.renormalize = router, bool(renormalize)
         self.aux_loss_coef, self.z_loss_coef, self.last_aux_loss = float(aux_loss_coef), float(z_loss_coef), None
+        # the group-limited gate (K13): only when one of its arguments is given
+        self.grouped = (score != "softmax" or expert_groups is not None or topk_groups is not None
+                        or routed_scale != 1.0 or bool(balance_bias))
+        if score not in GATE_SCORES:
+            raise ValueError(f"score {score!r} is not 'softmax' or 'sigmoid'")
+        if self.grouped and router != "fused":
+            raise ValueError("score, expert_groups, topk_groups, routed_scale and balance_bias need router='fused'")
+        if score == "sigmoid" and z_loss_coef:
+            raise ValueError("z_loss_coef needs the softmax score: the sigmoid score has no log-sum-exp")
+        if topk_groups is not None and expert_groups is None:
+            raise ValueError("topk_groups needs expert_groups")
+        self.score, self.routed_scale, self.balance_bias = score, float(routed_scale), bool(balance_bias)
+        self.expert_groups = 1 if expert_groups is None else expert_groups
+        self.topk_groups = self.expert_groups if topk_groups is None else topk_groups
+        self.last_counts = self.last_ids = self.last_group_ids = None
         p, r = comm.getSlaveNum(), comm.getRank()
         if num_experts % p:
             raise ValueError(f"num_experts {num_experts} is not a multiple of the {p} ranks")
         if not 1 <= top_k <= num_experts:
             raise ValueError("top_k must be in [1, num_experts]")
         self.comm, self.num_experts, self.top_k, self.operand = comm, num_experts, top_k, operand
+        if self.grouped:                           # what route_topk_grouped would refuse at the first forward
+            Gr, Kg = self.expert_groups, self.topk_groups
+            if isinstance(Gr, bool) or not isinstance(Gr, int) or Gr < 1 or num_experts % Gr:
+                raise ValueError(f"expert_groups {Gr!r} is not a positive int that divides num_experts = {num_experts}")
+            if isinstance(Kg, bool) or not isinstance(Kg, int) or not 1 <= Kg <= Gr:
+                raise ValueError(f"topk_groups {Kg!r} is not an int in [1, expert_groups = {Gr}]")
+            if top_k > Kg * (num_experts // Gr):
+                raise ValueError(f"top_k {top_k} is more than the {Kg} x {num_experts // Gr} experts of the chosen groups")
+            if not (self.routed_scale > 0.0 and self.routed_scale != float("inf")):
+                raise ValueError(f"routed_scale {routed_scale!r} is not finite and positive")
         if source_capacity is not None and capacity_factor is not None:
             raise ValueError("give source_capacity or capacity_factor, not both")
         self.capacity_factor, self.source_capacity, self.last_plan = capacity_factor, source_capacity, None
@@ -288,6 +505,8 @@ class ExpertParallelMoE(torch.nn.Module):
         def par(t):
             return torch.nn.Parameter(t.to(device=device, dtype=dtype).contiguous())
         self.router = par(full["router"])
+        if self.balance_bias:                      # replicated, moved by update_balance_bias alone
+            self.register_buffer("expert_bias", torch.zeros(num_experts, dtype=torch.float32, device=device))
         self.w1, self.b1 = par(full["w1"][lo:hi]), par(full["b1"][lo:hi])
         self.w2, self.b2 = par(full["w2"][lo:hi]), par(full["b2"][lo:hi])
 
@@ -314,8 +533,17 @@ class ExpertParallelMoE(torch.nn.Module):
     def route_fused(self, x: torch.Tensor):
         """:meth:`route` through :func:`route_topk`; stores ``last_aux_loss``."""
         T, E, K = x.shape[0], self.num_experts, self.top_k
-        res = route_topk(x @ self.router, K, self.renormalize, stats=self.aux_loss_coef != 0.0)
-        aux = res.lse.new_zeros(())
+        if self.grouped:
+            res = route_topk_grouped(x @ self.router, K, score=self.score,
+                                     bias=self.expert_bias if self.balance_bias else None, n_group=self.expert_groups,
+                                     topk_group=self.topk_groups, renormalize=self.renormalize, scale=self.routed_scale,
+                                     stats=self.aux_loss_coef != 0.0 or self.balance_bias)
+            self.last_ids, self.last_group_ids = res.ids, res.group_ids
+            if self.balance_bias:
+                self.last_counts = res.counts
+        else:
+            res = route_topk(x @ self.router, K, self.renormalize, stats=self.aux_loss_coef != 0.0)
+        aux = res.weights.new_zeros(())
         if T and self.aux_loss_coef != 0.0:
             aux = aux + self.aux_loss_coef * E * ((res.counts.to(torch.float32) / (T * K)) * (res.prob_sum / T)).sum()
         if T and self.z_loss_coef != 0.0:
@@ -341,6 +569,22 @@ class ExpertParallelMoE(torch.nn.Module):
             off += c
         y = torch.cat(outs) if outs else rows
         return combine_tokens(self.comm, y, plan, w.contiguous(), self.operand, self.combine_backward)
+
+    def update_balance_bias(self, rate: float) -> None:
+        """Auxiliary-loss-free load balancing, a collective, called after the optimizer step: the
+        last forward's ``counts`` are summed over the ranks (the communicator's int64 sum allreduce)
+        and ``expert_bias += rate * sign(mean(load) - load)``, so an expert under the mean load is
+        chosen more often from the next step on.  Every rank ends with the same bias bits."""
+        if not self.balance_bias:
+            raise ValueError("update_balance_bias needs balance_bias=True")
+        if self.last_counts is None:
+            raise ValueError("update_balance_bias needs a forward pass first")
+        load = self.last_counts.to(torch.int64).contiguous().clone()
+        if self.comm.getSlaveNum() > 1:
+            self.comm.allreduceArray(load, Operands.LONG_OPERAND(), Operators.Long.SUM, 0, load.numel())
+        with torch.no_grad():
+            load = load.to(torch.float32)
+            self.expert_bias.add_(torch.sign(load.mean() - load), alpha=float(rate))
 
     def sync_gradients(self) -> None:
         p = self.comm.getSlaveNum()

@@ -812,6 +812,125 @@ def moe_gate_backward(logits: torch.Tensor, lse: torch.Tensor, ids: torch.Tensor
     return out
 
 
+MOE_GATE_MAX_GROUPS = 32
+MOE_GATE_SCORES = ("softmax", "sigmoid")          # the C ABI's score argument is the index
+
+
+def _gate_group_args(fn: str, E: int, K: int, score, n_group, topk_group, scale) -> Tuple[int, int, int, float]:
+    """(score index, n_group, topk_group, scale) of a K13 call, checked as csrc/kernels/moe_gate_group.hip
+    checks them."""
+    if score not in MOE_GATE_SCORES:
+        raise ValueError(f"{fn}: score {score!r} is not 'softmax' or 'sigmoid'")
+    if isinstance(n_group, bool) or not isinstance(n_group, int) or not 1 <= n_group <= MOE_GATE_MAX_GROUPS or E % n_group:
+        raise ValueError(f"{fn}: n_group {n_group!r} is not an int in [1, {MOE_GATE_MAX_GROUPS}] that divides E = {E}")
+    if topk_group is None:
+        topk_group = n_group
+    if isinstance(topk_group, bool) or not isinstance(topk_group, int) or not 1 <= topk_group <= n_group:
+        raise ValueError(f"{fn}: topk_group {topk_group!r} is not an int in [1, n_group = {n_group}]")
+    if K > topk_group * (E // n_group):
+        raise ValueError(f"{fn}: top_k {K} is more than the {topk_group} x {E // n_group} experts of the chosen groups")
+    scale = float(scale)
+    if not (scale > 0.0 and scale != float("inf")):
+        raise ValueError(f"{fn}: scale {scale!r} is not finite and positive")
+    return MOE_GATE_SCORES.index(score), n_group, topk_group, scale
+
+
+def moe_gate_group_topk(logits: torch.Tensor, top_k: int, score: str = "sigmoid", bias: Optional[torch.Tensor] = None,
+                        n_group: int = 1, topk_group: Optional[int] = None, renormalize: bool = False,
+                        scale: float = 1.0, ids_dtype=torch.int64, stats: bool = False, stream=None, out=None):
+    """K13's forward over ``logits`` [T, E]: ``(weights, ids, lse, prob_sum, counts, group_ids)``.
+    The score s is the softmax or ``1 / (1 + exp(-l))``; a token first takes the ``topk_group`` of
+    the ``n_group`` contiguous expert groups with the largest sum of their two largest selection
+    scores ``s + bias`` (``group_ids`` int32 [T, topk_group], in that order), then its K experts
+    inside them, in the order (selection score descending, index ascending; the logits' own order
+    without a bias).  ``weights`` float32 [T, K] are the chosen s (not s + bias), divided by their
+    sum with ``renormalize``, times ``scale``.  ``lse`` is None for the sigmoid score; ``prob_sum``
+    and ``counts`` are None without ``stats``.  ``out``: the six tensors to write (None where the
+    call has none) instead of new ones.  Nothing is read back."""
+    fn = "moe_gate_group_topk"
+    _dev_check(logits, bias)
+    T, E, K = _gate_shape(fn, logits, top_k)
+    sc, Gr, Kg, scale = _gate_group_args(fn, E, K, score, n_group, topk_group, scale)
+    if ids_dtype not in (torch.int32, torch.int64):
+        raise ValueError(f"{fn}: ids_dtype must be int32 or int64")
+    if bias is not None and (bias.dtype != torch.float32 or tuple(bias.shape) != (E,) or not bias.is_contiguous()):
+        raise ValueError(f"{fn}: bias must be contiguous float32 [{E}]")
+    dev = logits.device
+    want = (((T, K), torch.float32), ((T, K), ids_dtype), ((T,), torch.float32) if sc == 0 else None,
+            ((E,), torch.float32) if stats else None, ((E,), torch.int64) if stats else None, ((T, Kg), torch.int32))
+    if out is None:
+        out = tuple(None if w is None else torch.empty(w[0], dtype=w[1], device=dev) for w in want)
+    else:
+        out = tuple(out)
+        if len(out) != 6 or any((t is not None) if w is None else (not isinstance(t, torch.Tensor) or tuple(t.shape) != w[0]
+                                                                    or t.dtype != w[1] or not t.is_contiguous())
+                                for t, w in zip(out, want)):
+            raise ValueError(f"{fn}: out must be (weights, ids, lse, prob_sum, counts, group_ids) of the call's shapes "
+                             "and dtypes, None where the call has none")
+        _dev_check(logits, *out)
+    weights, ids, lse, prob_sum, counts, group_ids = out
+    scratch = None
+    sb = 0
+    lib = native.hip()
+    dt = int(dtype_of_torch(logits.dtype))
+    if stats:
+        sb = lib.mp4x_moe_gate_group_scratch_bytes(dt, T, E)
+        scratch = torch.empty(max(sb, 1), dtype=torch.uint8, device=dev)
+    if T == 0 and not stats:
+        return out
+
+    def ptr(t):
+        return t.data_ptr() if (t is not None and T) else None
+    check(lib.mp4x_moe_gate_group_topk(dt, ptr(logits), bias.data_ptr() if bias is not None else None, T, E, K, Gr, Kg, sc,
+                                       int(bool(renormalize)), scale, ptr(weights), ptr(ids),
+                                       int(ids_dtype == torch.int64), ptr(group_ids), ptr(lse),
+                                       prob_sum.data_ptr() if stats else None, counts.data_ptr() if stats else None,
+                                       scratch.data_ptr() if stats else None, sb, stream_ptr(stream)),
+          "mp4x_moe_gate_group_topk")
+    return out
+
+
+def moe_gate_group_backward(logits: torch.Tensor, lse: Optional[torch.Tensor], ids: torch.Tensor, score: str = "sigmoid",
+                            renormalize: bool = False, scale: float = 1.0, g_weights: Optional[torch.Tensor] = None,
+                            g_lse: Optional[torch.Tensor] = None, g_prob_sum: Optional[torch.Tensor] = None,
+                            out: Optional[torch.Tensor] = None, stream=None):
+    """K13's backward: the gradient of ``logits`` (their dtype, one rounding) from the saved
+    ``logits``, ``ids`` and (softmax) ``lse`` of :func:`moe_gate_group_topk` and the gradients of
+    ``weights`` [T, K], ``lse`` [T] and ``prob_sum`` [E], all float32, each None for zeros.  The
+    sigmoid score has no ``lse``: ``lse`` and ``g_lse`` must be None."""
+    fn = "moe_gate_group_backward"
+    _dev_check(logits, lse, ids, g_weights, g_lse, g_prob_sum, out)
+    if ids.dim() != 2 or ids.dtype not in (torch.int32, torch.int64):
+        raise ValueError(f"{fn}: ids must be [T, K] in int32 or int64")
+    T, E, K = _gate_shape(fn, logits, int(ids.shape[1]))
+    sc, _, _, scale = _gate_group_args(fn, E, K, score, 1, 1, scale)
+    if ids.shape[0] != T:
+        raise ValueError(f"{fn}: {ids.shape[0]} rows of ids for {T} rows of logits")
+    for name, t, shape in (("lse", lse, (T,)), ("g_weights", g_weights, (T, K)), ("g_lse", g_lse, (T,)),
+                           ("g_prob_sum", g_prob_sum, (E,))):
+        if t is not None and (t.dtype != torch.float32 or tuple(t.shape) != shape):
+            raise ValueError(f"{fn}: {name} must be float32 {list(shape)}")
+    if sc == 0 and lse is None:
+        raise ValueError(f"{fn}: lse is missing")
+    if sc == 1 and (lse is not None or g_lse is not None):
+        raise ValueError(f"{fn}: the sigmoid score has no lse")
+    if out is None:
+        out = torch.empty_like(logits)
+    elif out.dtype != logits.dtype or out.shape != logits.shape:
+        raise ValueError(f"{fn}: out dtype / shape differ from the logits'")
+    if T == 0:
+        return out
+
+    def ptr(t):
+        return t.data_ptr() if t is not None else None
+    check(native.hip().mp4x_moe_gate_group_backward(int(dtype_of_torch(logits.dtype)), logits.data_ptr(), ptr(lse),
+                                                    ids.data_ptr(), int(ids.dtype == torch.int64), T, E, K, sc,
+                                                    int(bool(renormalize)), scale, ptr(g_weights), ptr(g_lse),
+                                                    ptr(g_prob_sum), out.data_ptr(), stream_ptr(stream)),
+          "mp4x_moe_gate_group_backward")
+    return out
+
+
 # int64 key sorts: rocPRIM's own dispatch (block sort + merge passes below 1 M items, whatever the
 # key width) or forced onesweep (csrc/kernels/sparse.hip OnesweepSort: ~27 us per 8-bit pass at
 # 200 k items).  Measured on MI355X (profiles/r6/sparse/sort_ab.jsonl): onesweep wins at <= 16 bits
