@@ -599,6 +599,75 @@ def grouped_mm_wgrad_torch(x: torch.Tensor, gy: torch.Tensor, table, want_bias: 
     return gw.to(x.dtype), (gb.to(x.dtype) if want_bias else None)
 
 
+# ---------------------------------------------------------------- the gated expert activation: its definition
+def _glu_segments(fn: str, pre: torch.Tensor, g_h: Optional[torch.Tensor], table) -> List[Tuple[int, int]]:
+    """The ``(first row, row count)`` segments somebody owns in ``pre`` flattened to ``[R, 2N]``, after
+    the checks a kernel's wrapper would make; reads the table on the host (the torch form only)."""
+    for name, t in (("pre", pre), ("g_h", g_h)):
+        if t is None and name != "pre":
+            continue
+        if not isinstance(t, torch.Tensor) or t.dtype not in DTYPES:
+            raise ValueError(f"{fn}: {name} must be a float32 / bfloat16 / float16 tensor")
+        if not t.is_contiguous():
+            raise ValueError(f"{fn}: {name} must be contiguous")
+        if t.dtype != pre.dtype or t.device != pre.device:
+            raise ValueError(f"{fn}: {name} must have pre's dtype and device")
+    if pre.dim() < 2 or pre.shape[-1] % 2:
+        raise ValueError(f"{fn}: pre must be [..., 2N]; its last dimension {tuple(pre.shape)[-1:]} is odd or missing")
+    if not isinstance(table, tuple) or not table or table[0] not in ("ragged", "padded"):
+        raise ValueError(f"{fn}: table must be ('ragged', offsets) or ('padded', valid, S)")
+    tt = table[1] if len(table) > 1 else None
+    if not isinstance(tt, torch.Tensor) or tt.dtype != torch.int64 or tt.device != pre.device:
+        raise ValueError(f"{fn}: table must hold an int64 tensor on pre's device")
+    if table[0] == "ragged" and (tt.dim() != 1 or tt.numel() < 1):
+        raise ValueError(f"{fn}: a ragged table is ('ragged', offsets [G + 1]) over pre [R, 2N]")
+    G = tt.numel() - 1 if table[0] == "ragged" else tt.shape[0]
+    try:
+        segs = _table_segments(table, pre, G)
+    except ValueError as e:
+        raise ValueError(f"{fn}: pre / table: {e}") from None
+    if g_h is not None and tuple(g_h.shape) != tuple(pre.shape[:-1]) + (pre.shape[-1] // 2,):
+        raise ValueError(f"{fn}: g_h must be {list(pre.shape[:-1]) + [pre.shape[-1] // 2]}, not {list(g_h.shape)}")
+    return [seg for group in segs for seg in group if seg[1] > 0]
+
+
+def glu_torch(pre: torch.Tensor, table) -> torch.Tensor:
+    """The definition of the gated (SwiGLU) expert activation in torch, and its CPU form: with ``gate
+    = pre[..., :N]`` and ``up = pre[..., N:]``, ``h = (g / (1 + exp(-g))) * u`` in float32 on the
+    exactly converted operands with one rounding, for the rows somebody owns along ``table``; +0 in
+    every row nobody owns (those rows of ``pre`` are never read).  It reads the table on the host;
+    a kernel for it must not."""
+    segs = _glu_segments("glu_torch", pre, None, table)
+    N = pre.shape[-1] // 2
+    flat = pre.reshape(_width(pre.shape[:-1]), 2 * N)
+    out = torch.zeros((flat.shape[0], N), dtype=pre.dtype, device=pre.device)
+    for lo, n in segs:
+        rows = flat[lo:lo + n].to(torch.float32)
+        g, u = rows[:, :N], rows[:, N:]
+        out[lo:lo + n] = ((g / (1.0 + torch.exp(-g))) * u).to(pre.dtype)
+    return out.view(tuple(pre.shape[:-1]) + (N,))
+
+
+def glu_backward_torch(pre: torch.Tensor, g_h: torch.Tensor, table) -> torch.Tensor:
+    """The closed-form backward of :func:`glu_torch` from the saved ``pre``: with ``s = 1 / (1 +
+    exp(-g))`` and ``sm = 1 / (1 + exp(g))`` (by that formula, never ``1 - s``), ``g_pre[..., :N] =
+    (g_h * u) * (s * (1 + g * sm))`` and ``g_pre[..., N:] = g_h * (g / (1 + exp(-g)))``, each with one
+    rounding; +0 in every row nobody owns, where neither ``pre`` nor ``g_h`` is read."""
+    segs = _glu_segments("glu_backward_torch", pre, g_h, table)
+    N = pre.shape[-1] // 2
+    R = _width(pre.shape[:-1])
+    flat, gf = pre.reshape(R, 2 * N), g_h.reshape(R, N)
+    out = torch.zeros_like(flat)
+    for lo, n in segs:
+        rows, d = flat[lo:lo + n].to(torch.float32), gf[lo:lo + n].to(torch.float32)
+        g, u = rows[:, :N], rows[:, N:]
+        den = 1.0 + torch.exp(-g)
+        s, sm = 1.0 / den, 1.0 / (1.0 + torch.exp(g))
+        out[lo:lo + n, :N] = ((d * u) * (s * (1.0 + g * sm))).to(pre.dtype)
+        out[lo:lo + n, N:] = (d * (g / den)).to(pre.dtype)
+    return out.view(pre.shape)
+
+
 # ---------------------------------------------------------------- the padded fixed-capacity layout
 def _check_source_capacity(source_capacity, capacity, capacity_factor):
     """The caller's contract, the same on every rank: refused before any work."""
