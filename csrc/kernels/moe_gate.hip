@@ -24,6 +24,9 @@
 //   backward  k_moe_gate_bwd   p_j = exp(l_j - lse) again from the saved logits and lse, the K
 //             chosen probabilities from K more (cached) loads, then the closed form of
 //             softmax + top-k + renormalisation + lse + prob_sum, rounded once to the logits' dtype.
+//             The same kernel is K13's backward (moe_gate_group.hip): a scale on the gate weights'
+//             gradient (1 here: exact) and, as a template argument, the sigmoid score, with
+//             d_j = sigmoid(l_j) * sigmoid(-l_j), no lse and no dot over the row.
 //
 // No floating-point atomics and no global atomics at all: every result is identical run to run.
 #include "moe_gate_common.hpp"
@@ -193,10 +196,13 @@ __global__ __launch_bounds__(kBlock) void k_moe_gate_stats(const float* __restri
 }
 
 
-template <int DT, int NV>
+// The backward of K10 (SIGMOID false) and of K13 (either score; the groups and the bias have no
+// gradient): the gradient of the gate weights is scaled by `scale`, the sigmoid score has no lse
+// and its columns do not depend on each other (no dot over the row).
+template <int DT, int NV, bool SIGMOID>
 __global__ __launch_bounds__(kBlock) void k_moe_gate_bwd(const void* __restrict__ logits, const float* __restrict__ lse,
                                                          const void* __restrict__ ids, int ids_are_i64, int64_t T,
-                                                         int E, int K, int G, int lgG, int vec, int renorm,
+                                                         int E, int K, int G, int lgG, int vec, int renorm, float scale,
                                                          const float* __restrict__ g_w, const float* __restrict__ g_lse,
                                                          const float* __restrict__ g_psum, void* __restrict__ g_logits) {
   using S = typename Elem<DT>::S;
@@ -219,11 +225,12 @@ __global__ __launch_bounds__(kBlock) void k_moe_gate_bwd(const void* __restrict_
     const bool valid = t < T;
     const int64_t tt = valid ? t : 0;                 // a group past T walks token 0 and stores nothing
     float x[VPL];
-    gate_load_row<DT, NV>(logits, tt, E, G, sub, vec != 0, true, -INFINITY, x);      // -inf past E: p = 0 there
-    const float l = lse[tt];
-    const float gl = g_lse ? g_lse[tt] : 0.0f;
+    gate_load_row<DT, NV>(logits, tt, E, G, sub, vec != 0, true, -INFINITY, x);      // -inf past E: score 0 there
+    const float l = SIGMOID ? 0.0f : lse[tt];
+    const float gl = (g_lse && !SIGMOID) ? g_lse[tt] : 0.0f;
 
-    // the chosen K: p_k = exp(l[id_k] - lse); the lanes of a group read the same (cached) words
+    // the chosen K: their scores again (softmax: p_k = exp(l[id_k] - lse)); the lanes of a group
+    // read the same (cached) words
     float pk[kGateMaxK], gq[kGateMaxK];
     int idk[kGateMaxK];
     float s = 0.0f;
@@ -234,7 +241,8 @@ __global__ __launch_bounds__(kBlock) void k_moe_gate_bwd(const void* __restrict_
       MP4X_DASSERT(id >= 0 && id < E);
       const bool ok = id >= 0 && id < E;              // an id outside the row takes no part and is never read through
       idk[k] = ok ? (int)id : -1;
-      pk[k] = ok ? expf(Elem<DT>::load(reinterpret_cast<const S*>(logits)[tt * E + idk[k]]) - l) : 0.0f;
+      const float lk = ok ? Elem<DT>::load(reinterpret_cast<const S*>(logits)[tt * E + idk[k]]) : 0.0f;
+      pk[k] = ok ? (SIGMOID ? gate_sigmoid(lk) : expf(lk - l)) : 0.0f;
       gq[k] = (g_w && ok) ? g_w[tt * K + k] : 0.0f;
       s += pk[k];
     }
@@ -251,13 +259,19 @@ __global__ __launch_bounds__(kBlock) void k_moe_gate_bwd(const void* __restrict_
         gq[k] = (gq[k] - dw) / s;
       }
     }
+#pragma unroll
+    for (int k = 0; k < kGateMaxK; ++k) {
+      if (k >= K) continue;
+      gq[k] *= scale;
+    }
 
     float p[VPL], gp[VPL];
     float dot = 0.0f;
 #pragma unroll
     for (int i = 0; i < VPL; ++i) {
       const int col = (sub + (i / W) * G) * W + (i % W);
-      p[i] = expf(x[i] - l);
+      // sigmoid: d = sigmoid(l) * sigmoid(-l), both by the forward's formula
+      p[i] = SIGMOID ? gate_sigmoid(x[i]) * gate_sigmoid(-x[i]) : expf(x[i] - l);
       float g = gps[i];
 #pragma unroll
       for (int k = 0; k < kGateMaxK; ++k) {
@@ -265,9 +279,11 @@ __global__ __launch_bounds__(kBlock) void k_moe_gate_bwd(const void* __restrict_
         g += idk[k] == col ? gq[k] : 0.0f;            // the ids of a token are distinct: one k at most
       }
       gp[i] = g;
-      dot += col < E ? g * p[i] : 0.0f;
+      if constexpr (!SIGMOID) dot += col < E ? g * p[i] : 0.0f;
     }
-    for (int off = G >> 1; off >= 1; off >>= 1) dot += __shfl_xor(dot, off);
+    if constexpr (!SIGMOID) {
+      for (int off = G >> 1; off >= 1; off >>= 1) dot += __shfl_xor(dot, off);
+    }
 
     if (!valid) continue;
     S* out = reinterpret_cast<S*>(g_logits) + t * E;
@@ -277,7 +293,10 @@ __global__ __launch_bounds__(kBlock) void k_moe_gate_bwd(const void* __restrict_
       if (c0 >= E) continue;
       float a[W];
 #pragma unroll
-      for (int j = 0; j < W; ++j) a[j] = p[v * W + j] * (gp[v * W + j] - dot) + gl * p[v * W + j];
+      for (int j = 0; j < W; ++j) {
+        const int i = v * W + j;
+        a[j] = SIGMOID ? p[i] * gp[i] : p[i] * (gp[i] - dot) + gl * p[i];
+      }
       if (vec) {
         *reinterpret_cast<u32x4*>(out + c0) = pack<DT, u32x4>(a);
       } else {
@@ -289,17 +308,34 @@ __global__ __launch_bounds__(kBlock) void k_moe_gate_bwd(const void* __restrict_
   }
 }
 
+int gate_backward(int dtype, const void* logits, const float* lse, const void* ids, int ids_are_i64, int64_t T, int E, int K,
+                  int sigmoid, int renormalize, float scale, const float* g_weights, const float* g_lse,
+                  const float* g_prob_sum, void* g_logits, void* stream) {
+  if (T == 0) return 0;
+  if (!logits || !g_logits || (((uintptr_t)logits | (uintptr_t)g_logits) & 15) || (!sigmoid && !lse) ||
+      ((uintptr_t)lse & 3) || !ids || ((uintptr_t)ids & (ids_are_i64 ? 7 : 3)) ||
+      (((uintptr_t)g_weights | (uintptr_t)g_lse | (uintptr_t)g_prob_sum) & 3))
+    return MP4X_E_BADARG;
+  const GateShape s = gate_shape(dtype, T, E);
+  hipStream_t st = (hipStream_t)stream;
+  return with_gate_dtype(dtype, [&](auto dtc) {
+    constexpr int DT = decltype(dtc)::value;
+    return with_gate_nv<DT>(s.NV, [&](auto nvc) {
+      constexpr int NV = decltype(nvc)::value;
+      const auto launch = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, dim3(s.nblk), dim3(kBlock), 0, st, logits, lse, ids, ids_are_i64, T, E, K, s.G, s.lgG,
+                           s.vec, renormalize != 0, scale, g_weights, g_lse, g_prob_sum, g_logits);
+      };
+      if (sigmoid) launch(k_moe_gate_bwd<DT, NV, true>);
+      else launch(k_moe_gate_bwd<DT, NV, false>);
+      return (int)hipGetLastError();
+    });
+  });
+}
+
 }  // namespace mp4x
 
 using namespace mp4x;
-
-namespace {
-int gate_args_ok(int dtype, int64_t T, int E, int K) {
-  if (int e = gate_dtype_ok(dtype)) return e;
-  if (E < 1 || E > kGateMaxE || K < 1 || K > kGateMaxK || K > E || T < 0 || T > INT32_MAX / 2 / K) return MP4X_E_BADARG;
-  return 0;
-}
-}  // namespace
 
 extern "C" size_t mp4x_moe_gate_scratch_bytes(int dtype, int64_t T, int E) {
   if (gate_dtype_ok(dtype) || E < 1 || E > kGateMaxE || T < 0) return 0;
@@ -311,67 +347,21 @@ extern "C" int mp4x_moe_gate_topk(int dtype, const void* logits, int64_t T, int 
                                   float* weights, void* ids, int ids_are_i64, float* lse, float* prob_sum,
                                   int64_t* counts, void* scratch, size_t scratch_bytes, void* stream) {
   if (int e = gate_args_ok(dtype, T, E, K)) return e;
-  const bool stats = prob_sum || counts;
-  if (stats && (!prob_sum || !counts || ((uintptr_t)prob_sum & 3) || ((uintptr_t)counts & 7))) return MP4X_E_BADARG;
-  hipStream_t st = (hipStream_t)stream;
-  const int scols = (E + kGateCols - 1) / kGateCols;
-  if (T == 0) {
-    if (!stats) return 0;
-    hipLaunchKernelGGL(k_moe_gate_stats, dim3(scols), dim3(kBlock), 0, st, (const float*)nullptr, (const int32_t*)nullptr, 0,
-                       E, prob_sum, counts);
-    return (int)hipGetLastError();
-  }
-  if (!logits || ((uintptr_t)logits & 15) || !weights || ((uintptr_t)weights & 3) || !ids ||
-      ((uintptr_t)ids & (ids_are_i64 ? 7 : 3)) || !lse || ((uintptr_t)lse & 3))
-    return MP4X_E_BADARG;
   const GateShape s = gate_shape(dtype, T, E);
-  float* psum_part = nullptr;
-  int32_t* cnt_part = nullptr;
-  if (stats) {
-    if (!scratch || ((uintptr_t)scratch & 255) || scratch_bytes < mp4x_moe_gate_scratch_bytes(dtype, T, E))
-      return MP4X_E_BADARG;
-    psum_part = (float*)scratch;
-    cnt_part = (int32_t*)((char*)scratch + gate_align((size_t)s.nblk * E * sizeof(float)));
-  }
-  const int e = with_gate_dtype(dtype, [&](auto dtc) {
-    constexpr int DT = decltype(dtc)::value;
-    return with_gate_nv<DT>(s.NV, [&](auto nvc) {
-      constexpr int NV = decltype(nvc)::value;
-      constexpr int VPL = NV * (16 / (int)sizeof(typename Elem<DT>::S));
-      if (stats) {
-        const size_t lds = (size_t)kBlock * VPL * sizeof(float) + (size_t)E * sizeof(int32_t);
-        hipLaunchKernelGGL((k_moe_gate_fwd<DT, NV, true>), dim3(s.nblk), dim3(kBlock), lds, st, logits, T, E, K, s.G, s.lgG,
-                           s.vec, renormalize != 0, weights, ids, ids_are_i64, lse, psum_part, cnt_part);
-      } else {
-        hipLaunchKernelGGL((k_moe_gate_fwd<DT, NV, false>), dim3(s.nblk), dim3(kBlock), 0, st, logits, T, E, K, s.G, s.lgG,
-                           s.vec, renormalize != 0, weights, ids, ids_are_i64, lse, psum_part, cnt_part);
-      }
-      return (int)hipGetLastError();
-    });
+  hipStream_t st = (hipStream_t)stream;
+  return gate_forward(dtype, s, logits, T, E, weights, ids, ids_are_i64, lse && !((uintptr_t)lse & 3), prob_sum, counts,
+                      scratch, scratch_bytes, st, [&](auto dtc, auto nvc, auto statsc, size_t lds, float* psum_part,
+                                                      int32_t* cnt_part) {
+    hipLaunchKernelGGL((k_moe_gate_fwd<decltype(dtc)::value, decltype(nvc)::value, decltype(statsc)::value>), dim3(s.nblk),
+                       dim3(kBlock), lds, st, logits, T, E, K, s.G, s.lgG, s.vec, renormalize != 0, weights, ids, ids_are_i64,
+                       lse, psum_part, cnt_part);
   });
-  if (e || !stats) return e;
-  hipLaunchKernelGGL(k_moe_gate_stats, dim3(scols), dim3(kBlock), 0, st, (const float*)psum_part, (const int32_t*)cnt_part,
-                     (int)s.nblk, E, prob_sum, counts);
-  return (int)hipGetLastError();
 }
 
 extern "C" int mp4x_moe_gate_backward(int dtype, const void* logits, const float* lse, const void* ids, int ids_are_i64,
                                       int64_t T, int E, int K, int renormalize, const float* g_weights,
                                       const float* g_lse, const float* g_prob_sum, void* g_logits, void* stream) {
   if (int e = gate_args_ok(dtype, T, E, K)) return e;
-  if (T == 0) return 0;
-  if (!logits || !g_logits || (((uintptr_t)logits | (uintptr_t)g_logits) & 15) || !lse || ((uintptr_t)lse & 3) || !ids ||
-      ((uintptr_t)ids & (ids_are_i64 ? 7 : 3)) || (((uintptr_t)g_weights | (uintptr_t)g_lse | (uintptr_t)g_prob_sum) & 3))
-    return MP4X_E_BADARG;
-  const GateShape s = gate_shape(dtype, T, E);
-  hipStream_t st = (hipStream_t)stream;
-  return with_gate_dtype(dtype, [&](auto dtc) {
-    constexpr int DT = decltype(dtc)::value;
-    return with_gate_nv<DT>(s.NV, [&](auto nvc) {
-      constexpr int NV = decltype(nvc)::value;
-      hipLaunchKernelGGL((k_moe_gate_bwd<DT, NV>), dim3(s.nblk), dim3(kBlock), 0, st, logits, lse, ids, ids_are_i64, T, E, K,
-                         s.G, s.lgG, s.vec, renormalize != 0, g_weights, g_lse, g_prob_sum, g_logits);
-      return (int)hipGetLastError();
-    });
-  });
+  return gate_backward(dtype, logits, lse, ids, ids_are_i64, T, E, K, 0, renormalize, 1.0f, g_weights, g_lse, g_prob_sum,
+                       g_logits, stream);
 }

@@ -1,7 +1,9 @@
 // What the two router-gate files share (moe_gate.hip: K10; moe_gate_group.hip: K13): the limits, the
-// order-preserving key, the 64-bit shuffle, the row load, the id load, the lane-group shape and the
-// dtype / NV dispatch.  Moved here from moe_gate.hip unchanged; k_moe_gate_stats stays defined there
-// and is only declared here.
+// order-preserving key, the 64-bit shuffle, the row load, the sigmoid, the id load, the lane-group
+// shape, the dtype / NV dispatch, the argument check and what a forward entry does around its launch
+// (gate_forward).  The two forward kernels are separate and each keeps its own text; the one
+// backward of both gates (k_moe_gate_bwd behind gate_backward) and k_moe_gate_stats are defined in
+// moe_gate.hip and declared here.
 #pragma once
 #include "common.hpp"
 
@@ -56,6 +58,8 @@ __device__ __forceinline__ void gate_load_row(const void* __restrict__ logits, i
   }
 }
 
+__device__ __forceinline__ float gate_sigmoid(float x) { return 1.0f / (1.0f + expf(-x)); }
+
 // prob_sum[e] / counts[e] from the nblk per-block partials; nblk == 0 writes zeros (moe_gate.hip).
 __global__ __launch_bounds__(kBlock) void k_moe_gate_stats(const float* __restrict__ psum_part,
                                                            const int32_t* __restrict__ cnt_part, int nblk, int E,
@@ -64,6 +68,12 @@ __global__ __launch_bounds__(kBlock) void k_moe_gate_stats(const float* __restri
 __device__ __forceinline__ int64_t gate_id(const void* __restrict__ ids, int is_i64, int64_t i) {
   return is_i64 ? reinterpret_cast<const int64_t*>(ids)[i] : (int64_t)reinterpret_cast<const int32_t*>(ids)[i];
 }
+
+// The backward of both gates (moe_gate.hip): k_moe_gate_bwd for the softmax (`sigmoid` 0: `lse` is
+// needed) or the sigmoid score, after the entry has checked dtype, T, E, K and scale.
+int gate_backward(int dtype, const void* logits, const float* lse, const void* ids, int ids_are_i64, int64_t T, int E, int K,
+                  int sigmoid, int renormalize, float scale, const float* g_weights, const float* g_lse,
+                  const float* g_prob_sum, void* g_logits, void* stream);
 
 }  // namespace mp4x
 
@@ -125,5 +135,56 @@ template <typename F> int with_gate_dtype(int dtype, F&& f) {
     case MP4X_F16: return f(IntC<MP4X_F16>{});
     default: return MP4X_E_UNSUPPORTED;
   }
+}
+
+int gate_args_ok(int dtype, int64_t T, int E, int K) {
+  if (int e = gate_dtype_ok(dtype)) return e;
+  if (E < 1 || E > kGateMaxE || K < 1 || K > kGateMaxK || K > E || T < 0 || T > INT32_MAX / 2 / K) return MP4X_E_BADARG;
+  return 0;
+}
+
+// What a forward entry does around its kernel, after its own argument checks: the statistics'
+// pointers (both or neither), T == 0 (zeros for the statistics, nothing else), the pointers every
+// forward has (`others_ok`: the entry's own, looked at with T > 0 only), the split of the scratch,
+// launch(IntC<DT>, IntC<NV>, STATS as a bool constant, LDS bytes, psum_part, cnt_part) on the shape
+// `s`, and k_moe_gate_stats over the per-block partials.
+template <typename F>
+int gate_forward(int dtype, const GateShape& s, const void* logits, int64_t T, int E, float* weights, void* ids,
+                 int ids_are_i64, bool others_ok, float* prob_sum, int64_t* counts, void* scratch, size_t scratch_bytes,
+                 hipStream_t st, F&& launch) {
+  const bool stats = prob_sum || counts;
+  if (stats && (!prob_sum || !counts || ((uintptr_t)prob_sum & 3) || ((uintptr_t)counts & 7))) return MP4X_E_BADARG;
+  const int scols = (E + kGateCols - 1) / kGateCols;
+  if (T == 0) {
+    if (!stats) return 0;
+    hipLaunchKernelGGL(k_moe_gate_stats, dim3(scols), dim3(kBlock), 0, st, (const float*)nullptr, (const int32_t*)nullptr, 0,
+                       E, prob_sum, counts);
+    return (int)hipGetLastError();
+  }
+  if (!logits || ((uintptr_t)logits & 15) || !weights || ((uintptr_t)weights & 3) || !ids ||
+      ((uintptr_t)ids & (ids_are_i64 ? 7 : 3)) || !others_ok)
+    return MP4X_E_BADARG;
+  float* psum_part = nullptr;
+  int32_t* cnt_part = nullptr;
+  if (stats) {
+    if (!scratch || ((uintptr_t)scratch & 255) || scratch_bytes < mp4x_moe_gate_scratch_bytes(dtype, T, E))
+      return MP4X_E_BADARG;
+    psum_part = (float*)scratch;
+    cnt_part = (int32_t*)((char*)scratch + gate_align((size_t)s.nblk * E * sizeof(float)));
+  }
+  const int e = with_gate_dtype(dtype, [&](auto dtc) {
+    constexpr int DT = decltype(dtc)::value;
+    return with_gate_nv<DT>(s.NV, [&](auto nvc) {
+      constexpr int VPL = decltype(nvc)::value * (16 / (int)sizeof(typename Elem<DT>::S));
+      const size_t lds = (size_t)kBlock * VPL * sizeof(float) + (size_t)E * sizeof(int32_t);
+      if (stats) launch(dtc, nvc, std::true_type{}, lds, psum_part, cnt_part);
+      else launch(dtc, nvc, std::false_type{}, (size_t)0, psum_part, cnt_part);
+      return (int)hipGetLastError();
+    });
+  });
+  if (e || !stats) return e;
+  hipLaunchKernelGGL(k_moe_gate_stats, dim3(scols), dim3(kBlock), 0, st, (const float*)psum_part, (const int32_t*)cnt_part,
+                     (int)s.nblk, E, prob_sum, counts);
+  return (int)hipGetLastError();
 }
 }  // namespace

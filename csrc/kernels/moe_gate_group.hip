@@ -21,7 +21,10 @@
 //   statistics K10's: lane partials over the wave's tokens, LDS in (wave, group) order, per-block
 //              partials to scratch, then k_moe_gate_stats.
 //
-// The backward is one pass as K10's, with d_j = sigmoid(l_j) * sigmoid(-l_j) for the sigmoid score.
+// Only this forward kernel lives here; it stays apart from K10's, which scores only its K chosen
+// columns and is the faster for it.  The backward is K10's k_moe_gate_bwd (moe_gate.hip, behind
+// gate_backward) with the scale and, as a template argument, the sigmoid score:
+// d_j = sigmoid(l_j) * sigmoid(-l_j).
 // No floating-point atomics and no global atomics: every result is identical run to run.
 #include <math.h>
 
@@ -31,8 +34,6 @@ namespace mp4x {
 
 constexpr int kGateMaxGroups = 32;
 constexpr int kGateGroupSlots = 16;   // group scores a lane keeps: ceil(Gr / G) <= 16 for every shape
-
-__device__ __forceinline__ float gate_sigmoid(float x) { return 1.0f / (1.0f + expf(-x)); }
 
 template <int DT, int NV, bool STATS>
 __global__ __launch_bounds__(kBlock) void k_moe_gate_group_fwd(
@@ -260,113 +261,6 @@ __global__ __launch_bounds__(kBlock) void k_moe_gate_group_fwd(
   }
 }
 
-template <int DT, int NV>
-__global__ __launch_bounds__(kBlock) void k_moe_gate_group_bwd(
-    const void* __restrict__ logits, const float* __restrict__ lse, const void* __restrict__ ids, int ids_are_i64, int64_t T,
-    int E, int K, int sigmoid, int G, int lgG, int vec, int renorm, float scale, const float* __restrict__ g_w,
-    const float* __restrict__ g_lse, const float* __restrict__ g_psum, void* __restrict__ g_logits) {
-  using S = typename Elem<DT>::S;
-  constexpr int W = 16 / sizeof(S);
-  constexpr int VPL = NV * W;
-  const int lane = threadIdx.x & 63;
-  const int grp = lane >> lgG, sub = lane & (G - 1), R = 64 >> lgG;
-  const int64_t wave = wave_id();
-  const int64_t nwaves = ((int64_t)gridDim.x * kBlock) >> 6;
-
-  float gps[VPL];                                     // g_psum of the lane's columns: the same for every token
-#pragma unroll
-  for (int i = 0; i < VPL; ++i) {
-    const int col = (sub + (i / W) * G) * W + (i % W);
-    gps[i] = (g_psum && col < E) ? g_psum[col] : 0.0f;
-  }
-
-  for (int64_t t0 = wave * R; t0 < T; t0 += nwaves * R) {
-    const int64_t t = t0 + grp;
-    const bool valid = t < T;
-    const int64_t tt = valid ? t : 0;                 // a group past T walks token 0 and stores nothing
-    float x[VPL];
-    gate_load_row<DT, NV>(logits, tt, E, G, sub, vec != 0, true, -INFINITY, x);      // -inf past E: score 0 there
-    const float l = sigmoid ? 0.0f : lse[tt];
-    const float gl = (g_lse && !sigmoid) ? g_lse[tt] : 0.0f;
-
-    // the chosen K: their scores again; the lanes of a group read the same (cached) words
-    float pk[kGateMaxK], gq[kGateMaxK];
-    int idk[kGateMaxK];
-    float s = 0.0f;
-#pragma unroll
-    for (int k = 0; k < kGateMaxK; ++k) {
-      if (k >= K) continue;
-      const int64_t id = gate_id(ids, ids_are_i64, tt * K + k);
-      MP4X_DASSERT(id >= 0 && id < E);
-      const bool ok = id >= 0 && id < E;              // an id outside the row takes no part and is never read through
-      idk[k] = ok ? (int)id : -1;
-      const float lk = ok ? Elem<DT>::load(reinterpret_cast<const S*>(logits)[tt * E + idk[k]]) : 0.0f;
-      pk[k] = ok ? (sigmoid ? gate_sigmoid(lk) : expf(lk - l)) : 0.0f;
-      gq[k] = (g_w && ok) ? g_w[tt * K + k] : 0.0f;
-      s += pk[k];
-    }
-    if (renorm) {
-      float dw = 0.0f;
-#pragma unroll
-      for (int k = 0; k < kGateMaxK; ++k) {
-        if (k >= K) continue;
-        dw += gq[k] * (pk[k] / s);
-      }
-#pragma unroll
-      for (int k = 0; k < kGateMaxK; ++k) {
-        if (k >= K) continue;
-        gq[k] = (gq[k] - dw) / s;
-      }
-    }
-#pragma unroll
-    for (int k = 0; k < kGateMaxK; ++k) {
-      if (k >= K) continue;
-      gq[k] *= scale;
-    }
-
-    float p[VPL], gp[VPL];
-    float dot = 0.0f;
-#pragma unroll
-    for (int i = 0; i < VPL; ++i) {
-      const int col = (sub + (i / W) * G) * W + (i % W);
-      // sigmoid: d = sigmoid(l) * sigmoid(-l), both by the forward's formula
-      p[i] = sigmoid ? gate_sigmoid(x[i]) * gate_sigmoid(-x[i]) : expf(x[i] - l);
-      float g = gps[i];
-#pragma unroll
-      for (int k = 0; k < kGateMaxK; ++k) {
-        if (k >= K) continue;
-        g += idk[k] == col ? gq[k] : 0.0f;            // the ids of a token are distinct: one k at most
-      }
-      gp[i] = g;
-      dot += col < E ? g * p[i] : 0.0f;
-    }
-    if (!sigmoid) {
-      for (int off = G >> 1; off >= 1; off >>= 1) dot += __shfl_xor(dot, off);
-    }
-
-    if (!valid) continue;
-    S* out = reinterpret_cast<S*>(g_logits) + t * E;
-#pragma unroll
-    for (int v = 0; v < NV; ++v) {
-      const int c0 = (sub + v * G) * W;
-      if (c0 >= E) continue;
-      float a[W];
-#pragma unroll
-      for (int j = 0; j < W; ++j) {
-        const int i = v * W + j;
-        a[j] = sigmoid ? p[i] * gp[i] : p[i] * (gp[i] - dot) + gl * p[i];
-      }
-      if (vec) {
-        *reinterpret_cast<u32x4*>(out + c0) = pack<DT, u32x4>(a);
-      } else {
-#pragma unroll
-        for (int j = 0; j < W; ++j)
-          if (c0 + j < E) out[c0 + j] = Elem<DT>::store(a[j]);
-      }
-    }
-  }
-}
-
 }  // namespace mp4x
 
 using namespace mp4x;
@@ -375,7 +269,7 @@ namespace {
 int gate_group_args_ok(int dtype, int64_t T, int E, int K, int score, int Gr, int Kg, float scale) {
   if (int e = gate_dtype_ok(dtype)) return e;
   if (score != 0 && score != 1) return MP4X_E_UNSUPPORTED;
-  if (E < 1 || E > kGateMaxE || K < 1 || K > kGateMaxK || K > E || T < 0 || T > INT32_MAX / 2 / K) return MP4X_E_BADARG;
+  if (int e = gate_args_ok(dtype, T, E, K)) return e;
   if (Gr < 1 || Gr > kGateMaxGroups || E % Gr || Kg < 1 || Kg > Gr || K > (int64_t)Kg * (E / Gr)) return MP4X_E_BADARG;
   if (!(scale > 0.0f) || !std::isfinite(scale)) return MP4X_E_BADARG;
   return 0;
@@ -383,9 +277,7 @@ int gate_group_args_ok(int dtype, int64_t T, int E, int K, int score, int Gr, in
 }  // namespace
 
 extern "C" size_t mp4x_moe_gate_group_scratch_bytes(int dtype, int64_t T, int E) {
-  if (gate_dtype_ok(dtype) || E < 1 || E > kGateMaxE || T < 0) return 0;
-  const GateShape s = gate_shape(dtype, T, E);
-  return gate_align((size_t)s.nblk * E * sizeof(float)) + gate_align((size_t)s.nblk * E * sizeof(int32_t));
+  return mp4x_moe_gate_scratch_bytes(dtype, T, E);
 }
 
 extern "C" int mp4x_moe_gate_group_topk(int dtype, const void* logits, const float* bias, int64_t T, int E, int K,
@@ -394,53 +286,17 @@ extern "C" int mp4x_moe_gate_group_topk(int dtype, const void* logits, const flo
                                         float* prob_sum, int64_t* counts, void* scratch, size_t scratch_bytes,
                                         void* stream) {
   if (int e = gate_group_args_ok(dtype, T, E, K, score, n_group, topk_group, scale)) return e;
-  const bool stats = prob_sum || counts;
-  if (stats && (!prob_sum || !counts || ((uintptr_t)prob_sum & 3) || ((uintptr_t)counts & 7))) return MP4X_E_BADARG;
   if (((uintptr_t)bias | (uintptr_t)group_ids | (uintptr_t)lse) & 3) return MP4X_E_BADARG;
-  hipStream_t st = (hipStream_t)stream;
-  const int scols = (E + kGateCols - 1) / kGateCols;
-  if (T == 0) {
-    if (!stats) return 0;
-    hipLaunchKernelGGL(k_moe_gate_stats, dim3(scols), dim3(kBlock), 0, st, (const float*)nullptr, (const int32_t*)nullptr, 0,
-                       E, prob_sum, counts);
-    return (int)hipGetLastError();
-  }
-  if (!logits || ((uintptr_t)logits & 15) || !weights || ((uintptr_t)weights & 3) || !ids ||
-      ((uintptr_t)ids & (ids_are_i64 ? 7 : 3)) || (score == 0 && !lse))
-    return MP4X_E_BADARG;
   const GateShape s = gate_shape(dtype, T, E);
-  if (((n_group + s.G - 1) >> s.lgG) > kGateGroupSlots) return MP4X_E_BADARG;      // no shape reaches this
-  float* psum_part = nullptr;
-  int32_t* cnt_part = nullptr;
-  if (stats) {
-    if (!scratch || ((uintptr_t)scratch & 255) || scratch_bytes < mp4x_moe_gate_group_scratch_bytes(dtype, T, E))
-      return MP4X_E_BADARG;
-    psum_part = (float*)scratch;
-    cnt_part = (int32_t*)((char*)scratch + gate_align((size_t)s.nblk * E * sizeof(float)));
-  }
+  const bool others_ok = (score != 0 || lse) && ((n_group + s.G - 1) >> s.lgG) <= kGateGroupSlots;   // every shape has the slots
+  hipStream_t st = (hipStream_t)stream;
   const int n = E / n_group;
-  const int e = with_gate_dtype(dtype, [&](auto dtc) {
-    constexpr int DT = decltype(dtc)::value;
-    return with_gate_nv<DT>(s.NV, [&](auto nvc) {
-      constexpr int NV = decltype(nvc)::value;
-      constexpr int VPL = NV * (16 / (int)sizeof(typename Elem<DT>::S));
-      if (stats) {
-        const size_t lds = (size_t)kBlock * VPL * sizeof(float) + (size_t)E * sizeof(int32_t);
-        hipLaunchKernelGGL((k_moe_gate_group_fwd<DT, NV, true>), dim3(s.nblk), dim3(kBlock), lds, st, logits, bias, T, E, K,
-                           n_group, topk_group, n, score, s.G, s.lgG, s.vec, renormalize != 0, scale, weights, ids,
-                           ids_are_i64, group_ids, lse, psum_part, cnt_part);
-      } else {
-        hipLaunchKernelGGL((k_moe_gate_group_fwd<DT, NV, false>), dim3(s.nblk), dim3(kBlock), 0, st, logits, bias, T, E, K,
-                           n_group, topk_group, n, score, s.G, s.lgG, s.vec, renormalize != 0, scale, weights, ids,
-                           ids_are_i64, group_ids, lse, psum_part, cnt_part);
-      }
-      return (int)hipGetLastError();
-    });
+  return gate_forward(dtype, s, logits, T, E, weights, ids, ids_are_i64, others_ok, prob_sum, counts, scratch, scratch_bytes,
+                      st, [&](auto dtc, auto nvc, auto statsc, size_t lds, float* psum_part, int32_t* cnt_part) {
+    hipLaunchKernelGGL((k_moe_gate_group_fwd<decltype(dtc)::value, decltype(nvc)::value, decltype(statsc)::value>),
+                       dim3(s.nblk), dim3(kBlock), lds, st, logits, bias, T, E, K, n_group, topk_group, n, score, s.G, s.lgG,
+                       s.vec, renormalize != 0, scale, weights, ids, ids_are_i64, group_ids, lse, psum_part, cnt_part);
   });
-  if (e || !stats) return e;
-  hipLaunchKernelGGL(k_moe_gate_stats, dim3(scols), dim3(kBlock), 0, st, (const float*)psum_part, (const int32_t*)cnt_part,
-                     (int)s.nblk, E, prob_sum, counts);
-  return (int)hipGetLastError();
 }
 
 extern "C" int mp4x_moe_gate_group_backward(int dtype, const void* logits, const float* lse, const void* ids,
@@ -448,20 +304,6 @@ extern "C" int mp4x_moe_gate_group_backward(int dtype, const void* logits, const
                                             float scale, const float* g_weights, const float* g_lse,
                                             const float* g_prob_sum, void* g_logits, void* stream) {
   if (int e = gate_group_args_ok(dtype, T, E, K, score, 1, 1, scale)) return e;
-  if (T == 0) return 0;
-  if (!logits || !g_logits || (((uintptr_t)logits | (uintptr_t)g_logits) & 15) || (score == 0 && !lse) ||
-      ((uintptr_t)lse & 3) || !ids || ((uintptr_t)ids & (ids_are_i64 ? 7 : 3)) ||
-      (((uintptr_t)g_weights | (uintptr_t)g_lse | (uintptr_t)g_prob_sum) & 3))
-    return MP4X_E_BADARG;
-  const GateShape s = gate_shape(dtype, T, E);
-  hipStream_t st = (hipStream_t)stream;
-  return with_gate_dtype(dtype, [&](auto dtc) {
-    constexpr int DT = decltype(dtc)::value;
-    return with_gate_nv<DT>(s.NV, [&](auto nvc) {
-      constexpr int NV = decltype(nvc)::value;
-      hipLaunchKernelGGL((k_moe_gate_group_bwd<DT, NV>), dim3(s.nblk), dim3(kBlock), 0, st, logits, lse, ids, ids_are_i64, T,
-                         E, K, score, s.G, s.lgG, s.vec, renormalize != 0, scale, g_weights, g_lse, g_prob_sum, g_logits);
-      return (int)hipGetLastError();
-    });
-  });
+  return gate_backward(dtype, logits, lse, ids, ids_are_i64, T, E, K, score, renormalize, scale, g_weights, g_lse,
+                       g_prob_sum, g_logits, stream);
 }

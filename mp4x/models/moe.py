@@ -130,24 +130,9 @@ def _sum_in_k_order(q: torch.Tensor) -> torch.Tensor:
 
 def gate_forward_torch(logits: torch.Tensor, top_k: int, renormalize: bool, ids_dtype, stats: bool):
     """The definition of the gate in torch (float32 on the exactly converted logits): what K10
-    computes, for host tensors and for shapes outside the kernel's range."""
-    lg = logits.to(torch.float32)
-    T, E = lg.shape
-    # (logit descending, index ascending): the stable sort keeps equal logits in index order
-    ids = torch.sort(lg, dim=-1, descending=True, stable=True).indices[:, :top_k]
-    m = lg.max(dim=-1, keepdim=True).values if T else lg.new_zeros((0, 1))
-    ex = torch.exp(lg - m)
-    total = ex.sum(dim=-1, keepdim=True)
-    lse = (m + torch.log(total)).squeeze(-1)
-    p = ex / total
-    w = p.gather(1, ids)
-    if renormalize:
-        w = w / _sum_in_k_order(w).unsqueeze(1)
-    prob_sum = counts = None
-    if stats:
-        prob_sum = p.sum(dim=0)
-        counts = torch.bincount(ids.reshape(-1), minlength=E)
-    return w, ids.to(ids_dtype), lse, prob_sum, counts
+    computes, for host tensors and for shapes outside the kernel's range.  It is the group-limited
+    definition with the softmax score, no bias, one group and scale 1, bit for bit."""
+    return gate_group_forward_torch(logits, top_k, "softmax", None, 1, 1, renormalize, 1.0, ids_dtype, stats)[:5]
 
 
 def gate_backward_torch(logits: torch.Tensor, lse: torch.Tensor, ids: torch.Tensor, renormalize: bool,
@@ -155,55 +140,12 @@ def gate_backward_torch(logits: torch.Tensor, lse: torch.Tensor, ids: torch.Tens
                         g_prob_sum: Optional[torch.Tensor]) -> torch.Tensor:
     """The closed-form backward of the gate in torch, from the saved logits, lse and ids; an absent
     gradient counts as zero.  One rounding to the logits' dtype."""
-    lg = logits.to(torch.float32)
-    ids = ids.to(torch.int64)
-    p = torch.exp(lg - lse.unsqueeze(1))
-    gp = torch.zeros_like(p) if g_prob_sum is None else g_prob_sum.unsqueeze(0).expand_as(p).clone()
-    if g_weights is not None:
-        gq = g_weights
-        if renormalize:
-            q = p.gather(1, ids)
-            s = _sum_in_k_order(q).unsqueeze(1)
-            gq = (g_weights - _sum_in_k_order(g_weights * (q / s)).unsqueeze(1)) / s
-        gp.scatter_add_(1, ids, gq)
-    dot = (gp * p).sum(dim=-1, keepdim=True)
-    g = p * (gp - dot)
-    if g_lse is not None:
-        g = g + g_lse.unsqueeze(1) * p
-    return g.to(logits.dtype)
+    return gate_group_backward_torch(logits, lse, ids, "softmax", renormalize, 1.0, g_weights, g_lse, g_prob_sum)
 
 
 def _gate_is_fused(logits: torch.Tensor, top_k: int) -> bool:
     return (logits.is_cuda and logits.dtype in (torch.float32, torch.bfloat16, torch.float16)
             and 1 <= logits.shape[1] <= GATE_MAX_EXPERTS and top_k <= GATE_MAX_TOP_K)
-
-
-class _RouteTopK(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, logits, top_k, renormalize, ids_dtype, stats):
-        logits = logits.contiguous()
-        ctx.fused = _gate_is_fused(logits, top_k)
-        if ctx.fused:
-            from ..ops import device_ops
-            w, ids, lse, prob_sum, counts = device_ops.moe_gate_topk(logits, top_k, renormalize, ids_dtype, stats)
-        else:
-            w, ids, lse, prob_sum, counts = gate_forward_torch(logits, top_k, renormalize, ids_dtype, stats)
-        ctx.renormalize = renormalize
-        ctx.save_for_backward(logits, lse, ids)
-        ctx.set_materialize_grads(False)
-        ctx.mark_non_differentiable(*(t for t in (ids, counts) if t is not None))
-        return w, ids, lse, prob_sum, counts
-
-    @staticmethod
-    def backward(ctx, g_w, _g_ids, g_lse, g_psum, _g_counts):
-        logits, lse, ids = ctx.saved_tensors
-        g_w, g_lse, g_psum = (None if g is None else g.to(torch.float32).contiguous() for g in (g_w, g_lse, g_psum))
-        if ctx.fused:
-            from ..ops import device_ops
-            g = device_ops.moe_gate_backward(logits, lse, ids, ctx.renormalize, g_w, g_lse, g_psum)
-        else:
-            g = gate_backward_torch(logits, lse, ids, ctx.renormalize, g_w, g_lse, g_psum)
-        return g, None, None, None, None
 
 
 def route_topk(logits: torch.Tensor, top_k: int, renormalize: bool = False, ids_dtype=torch.int64,
@@ -222,7 +164,8 @@ def route_topk(logits: torch.Tensor, top_k: int, renormalize: bool = False, ids_
         raise ValueError(f"route_topk: top_k {top_k!r} is not an int in [1, E = {logits.shape[1]}]")
     if ids_dtype not in (torch.int32, torch.int64):
         raise ValueError("route_topk: ids_dtype must be int32 or int64")
-    return GateResult(*_RouteTopK.apply(logits, top_k, bool(renormalize), ids_dtype, bool(stats)))
+    return GateResult(*_RouteTopK.apply(logits, None, top_k, "softmax", 1, 1, bool(renormalize), 1.0, ids_dtype, bool(stats),
+                                        False)[:5])
 
 
 # ---------------------------------------------------------------- the group-limited router gate (K13)
@@ -323,19 +266,28 @@ def _gate_group_is_fused(logits: torch.Tensor, top_k: int, n_group: int) -> bool
     return _gate_is_fused(logits, top_k) and n_group <= GATE_MAX_GROUPS
 
 
-class _RouteTopKGrouped(torch.autograd.Function):
+class _RouteTopK(torch.autograd.Function):
+    """Both gates.  ``grouped`` says which device ops a GPU tensor goes to: K13's for
+    :func:`route_topk_grouped`, K10's (no score or group pass: the faster forward) for :func:`route_topk`,
+    which passes the softmax score, no bias, one group and scale 1.  Anywhere else it is the one
+    definition in torch."""
+
     @staticmethod
-    def forward(ctx, logits, bias, top_k, score, n_group, topk_group, renormalize, scale, ids_dtype, stats):
+    def forward(ctx, logits, bias, top_k, score, n_group, topk_group, renormalize, scale, ids_dtype, stats, grouped):
         logits = logits.contiguous()
-        ctx.fused = _gate_group_is_fused(logits, top_k, n_group)
-        if ctx.fused:
-            from ..ops import device_ops
-            w, ids, lse, prob_sum, counts, group_ids = device_ops.moe_gate_group_topk(
-                logits, top_k, score, bias, n_group, topk_group, renormalize, scale, ids_dtype, stats)
+        ctx.fused = _gate_group_is_fused(logits, top_k, n_group) if grouped else _gate_is_fused(logits, top_k)
+        if not ctx.fused:
+            out = gate_group_forward_torch(logits, top_k, score, bias, n_group, topk_group, renormalize, scale, ids_dtype,
+                                           stats)
         else:
-            w, ids, lse, prob_sum, counts, group_ids = gate_group_forward_torch(
-                logits, top_k, score, bias, n_group, topk_group, renormalize, scale, ids_dtype, stats)
-        ctx.score, ctx.renormalize, ctx.scale = score, renormalize, scale
+            from ..ops import device_ops
+            if grouped:
+                out = device_ops.moe_gate_group_topk(logits, top_k, score, bias, n_group, topk_group, renormalize, scale,
+                                                     ids_dtype, stats)
+            else:
+                out = device_ops.moe_gate_topk(logits, top_k, renormalize, ids_dtype, stats) + (None,)
+        w, ids, lse, prob_sum, counts, group_ids = out
+        ctx.score, ctx.renormalize, ctx.scale, ctx.grouped = score, renormalize, scale, grouped
         ctx.save_for_backward(logits, lse, ids)
         ctx.set_materialize_grads(False)
         ctx.mark_non_differentiable(*(t for t in (ids, counts, group_ids) if t is not None))
@@ -345,13 +297,18 @@ class _RouteTopKGrouped(torch.autograd.Function):
     def backward(ctx, g_w, _g_ids, g_lse, g_psum, _g_counts, _g_groups):
         logits, lse, ids = ctx.saved_tensors
         g_w, g_lse, g_psum = (None if g is None else g.to(torch.float32).contiguous() for g in (g_w, g_lse, g_psum))
-        if ctx.fused:
-            from ..ops import device_ops
-            g = device_ops.moe_gate_group_backward(logits, lse, ids, ctx.score, ctx.renormalize, ctx.scale, g_w, g_lse,
-                                                   g_psum)
-        else:
+        if not ctx.fused:
             g = gate_group_backward_torch(logits, lse, ids, ctx.score, ctx.renormalize, ctx.scale, g_w, g_lse, g_psum)
-        return (g,) + (None,) * 9
+        else:
+            from ..ops import device_ops
+            if ctx.grouped:
+                g = device_ops.moe_gate_group_backward(logits, lse, ids, ctx.score, ctx.renormalize, ctx.scale, g_w, g_lse,
+                                                       g_psum)
+            else:
+                g = device_ops.moe_gate_backward(logits, lse, ids, ctx.renormalize, g_w, g_lse, g_psum)
+        return (g,) + (None,) * 10
+
+
 
 
 def route_topk_grouped(logits: torch.Tensor, top_k: int, *, score: str = "sigmoid", bias: Optional[torch.Tensor] = None,
@@ -372,34 +329,23 @@ def route_topk_grouped(logits: torch.Tensor, top_k: int, *, score: str = "sigmoi
     On a GPU tensor with ``E <= 2048``, ``top_k <= 16`` and ``n_group <= 32`` forward and backward are
     the fused K13 kernels (no host synchronisation, bit-reproducible); anywhere else they are the
     same definition in torch."""
+    from ..ops.device_ops import gate_group_args
     fn = "route_topk_grouped"
     if logits.dim() != 2 or not logits.is_floating_point():
         raise ValueError(f"{fn}: logits must be a floating-point [T, E] tensor")
     E = logits.shape[1]
     if isinstance(top_k, bool) or not isinstance(top_k, int) or not 1 <= top_k <= E:
         raise ValueError(f"{fn}: top_k {top_k!r} is not an int in [1, E = {E}]")
-    if score not in GATE_SCORES:
-        raise ValueError(f"{fn}: score {score!r} is not 'softmax' or 'sigmoid'")
-    if isinstance(n_group, bool) or not isinstance(n_group, int) or n_group < 1 or E % n_group:
-        raise ValueError(f"{fn}: n_group {n_group!r} is not a positive int that divides E = {E}")
-    if topk_group is None:
-        topk_group = n_group
-    if isinstance(topk_group, bool) or not isinstance(topk_group, int) or not 1 <= topk_group <= n_group:
-        raise ValueError(f"{fn}: topk_group {topk_group!r} is not an int in [1, n_group = {n_group}]")
-    if top_k > topk_group * (E // n_group):
-        raise ValueError(f"{fn}: top_k {top_k} is more than the {topk_group} x {E // n_group} experts of the chosen groups")
+    n_group, topk_group, scale = gate_group_args(f"{fn}: ", E, top_k, score, n_group, topk_group, scale)
     if bias is not None:
         if (not isinstance(bias, torch.Tensor) or bias.dtype != torch.float32 or tuple(bias.shape) != (E,)
                 or bias.device != logits.device):
             raise ValueError(f"{fn}: bias must be a float32 [{E}] tensor on the logits' device")
         bias = bias.detach().contiguous()
-    scale = float(scale)
-    if not (scale > 0.0 and scale != float("inf")):
-        raise ValueError(f"{fn}: scale {scale!r} is not finite and positive")
     if ids_dtype not in (torch.int32, torch.int64):
         raise ValueError(f"{fn}: ids_dtype must be int32 or int64")
-    return GroupedGateResult(*_RouteTopKGrouped.apply(logits, bias, top_k, score, n_group, topk_group, bool(renormalize),
-                                                      scale, ids_dtype, bool(stats)))
+    return GroupedGateResult(*_RouteTopK.apply(logits, bias, top_k, score, n_group, topk_group, bool(renormalize), scale,
+                                               ids_dtype, bool(stats), True))
 
 
 class ExpertParallelMoE(torch.nn.Module):
@@ -466,8 +412,10 @@ class ExpertParallelMoE(torch.nn.Module):
         # the group-limited gate (K13): only when one of its arguments is given
         self.grouped = (score != "softmax" or expert_groups is not None or topk_groups is not None
                         or routed_scale != 1.0 or bool(balance_bias))
-        if score not in GATE_SCORES:
-            raise ValueError(f"score {score!r} is not 'softmax' or 'sigmoid'")
+        if self.grouped:                           # what route_topk_grouped would refuse at the first forward
+            from ..ops.device_ops import gate_group_args
+            gate_group_args("", num_experts, top_k, score, 1 if expert_groups is None else expert_groups, topk_groups,
+                            routed_scale, names=("expert_groups", "topk_groups", "routed_scale", "num_experts"))
         if self.grouped and router != "fused":
             raise ValueError("score, expert_groups, topk_groups, routed_scale and balance_bias need router='fused'")
         if score == "sigmoid" and z_loss_coef:
@@ -484,16 +432,6 @@ class ExpertParallelMoE(torch.nn.Module):
         if not 1 <= top_k <= num_experts:
             raise ValueError("top_k must be in [1, num_experts]")
         self.comm, self.num_experts, self.top_k, self.operand = comm, num_experts, top_k, operand
-        if self.grouped:                           # what route_topk_grouped would refuse at the first forward
-            Gr, Kg = self.expert_groups, self.topk_groups
-            if isinstance(Gr, bool) or not isinstance(Gr, int) or Gr < 1 or num_experts % Gr:
-                raise ValueError(f"expert_groups {Gr!r} is not a positive int that divides num_experts = {num_experts}")
-            if isinstance(Kg, bool) or not isinstance(Kg, int) or not 1 <= Kg <= Gr:
-                raise ValueError(f"topk_groups {Kg!r} is not an int in [1, expert_groups = {Gr}]")
-            if top_k > Kg * (num_experts // Gr):
-                raise ValueError(f"top_k {top_k} is more than the {Kg} x {num_experts // Gr} experts of the chosen groups")
-            if not (self.routed_scale > 0.0 and self.routed_scale != float("inf")):
-                raise ValueError(f"routed_scale {routed_scale!r} is not finite and positive")
         if source_capacity is not None and capacity_factor is not None:
             raise ValueError("give source_capacity or capacity_factor, not both")
         self.capacity_factor, self.source_capacity, self.last_plan = capacity_factor, source_capacity, None

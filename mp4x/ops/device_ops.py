@@ -733,6 +733,63 @@ def _gate_shape(fn: str, logits: torch.Tensor, top_k) -> Tuple[int, int, int]:
     return T, E, top_k
 
 
+def _ptr(t: Optional[torch.Tensor], on=True):
+    """The address of ``t``, None for no tensor or with ``on`` false (a call with no token passes none)."""
+    return t.data_ptr() if (t is not None and on) else None
+
+
+def _gate_outputs(fn: str, logits: torch.Tensor, want, out, names: str):
+    """The tensors a gate forward writes: new ones of ``want`` (a ``(shape, dtype)`` each, None where
+    the call has none), or ``out`` checked against it; an entry the call has none for is not looked at."""
+    if out is None:
+        return tuple(None if w is None else torch.empty(w[0], dtype=w[1], device=logits.device) for w in want)
+    out = tuple(out)
+    if len(out) != len(want) or any(w is not None and (not isinstance(t, torch.Tensor) or tuple(t.shape) != w[0]
+                                                       or t.dtype != w[1] or not t.is_contiguous())
+                                    for t, w in zip(out, want)):
+        raise ValueError(f"{fn}: out must be ({names}) of the call's shapes and dtypes")
+    _dev_check(logits, *(t for t, w in zip(out, want) if w is not None))
+    return out
+
+
+def _gate_scratch(scratch_bytes, dt: int, T: int, E: int, stats: bool, device):
+    """(tensor, bytes) of the statistics' scratch by the entry's own ``scratch_bytes``; (None, 0)
+    without ``stats``."""
+    if not stats:
+        return None, 0
+    sb = scratch_bytes(dt, T, E)
+    return torch.empty(max(sb, 1), dtype=torch.uint8, device=device), sb
+
+
+def _gate_backward(fn: str, logits, lse, ids, sigmoid: bool, g_weights, g_lse, g_prob_sum, out, call):
+    """What both gate backwards do around their C entry: the tensor checks (the softmax score needs
+    ``lse``, the sigmoid score has none), ``out``, nothing to do for no token, then
+    ``call((dtype, logits, lse, ids, ids_are_i64, T, E, K), (g_weights, g_lse, g_prob_sum, out))`` with
+    the addresses in the entry's order."""
+    _dev_check(logits, lse, ids, g_weights, g_lse, g_prob_sum, out)
+    if ids.dim() != 2 or ids.dtype not in (torch.int32, torch.int64):
+        raise ValueError(f"{fn}: ids must be [T, K] in int32 or int64")
+    T, E, K = _gate_shape(fn, logits, int(ids.shape[1]))
+    if ids.shape[0] != T:
+        raise ValueError(f"{fn}: {ids.shape[0]} rows of ids for {T} rows of logits")
+    for name, t, shape in (("lse", lse, (T,)), ("g_weights", g_weights, (T, K)), ("g_lse", g_lse, (T,)),
+                           ("g_prob_sum", g_prob_sum, (E,))):
+        if t is not None and (t.dtype != torch.float32 or tuple(t.shape) != shape):
+            raise ValueError(f"{fn}: {name} must be float32 {list(shape)}")
+    if not sigmoid and lse is None:
+        raise ValueError(f"{fn}: lse is missing")
+    if sigmoid and (lse is not None or g_lse is not None):
+        raise ValueError(f"{fn}: the sigmoid score has no lse")
+    if out is None:
+        out = torch.empty_like(logits)
+    elif out.dtype != logits.dtype or out.shape != logits.shape:
+        raise ValueError(f"{fn}: out dtype / shape differ from the logits'")
+    if T:
+        call((int(dtype_of_torch(logits.dtype)), logits.data_ptr(), _ptr(lse), ids.data_ptr(), int(ids.dtype == torch.int64),
+              T, E, K), (_ptr(g_weights), _ptr(g_lse), _ptr(g_prob_sum), out.data_ptr()))
+    return out
+
+
 def moe_gate_topk(logits: torch.Tensor, top_k: int, renormalize: bool = False, ids_dtype=torch.int64,
                   stats: bool = False, stream=None, out=None):
     """K10's forward over ``logits`` [T, E]: ``(weights, ids, lse, prob_sum, counts)``.  ``ids``
@@ -747,26 +804,14 @@ def moe_gate_topk(logits: torch.Tensor, top_k: int, renormalize: bool = False, i
     T, E, K = _gate_shape(fn, logits, top_k)
     if ids_dtype not in (torch.int32, torch.int64):
         raise ValueError(f"{fn}: ids_dtype must be int32 or int64")
-    dev = logits.device
-    want = (((T, K), torch.float32), ((T, K), ids_dtype), ((T,), torch.float32), ((E,), torch.float32),
-            ((E,), torch.int64))[:5 if stats else 3]
-    if out is None:
-        out = tuple(torch.empty(shape, dtype=dt, device=dev) for shape, dt in want)
-    else:
-        out = tuple(out)
-        if len(out) != 5 or any(not isinstance(t, torch.Tensor) or tuple(t.shape) != shape or t.dtype != dt
-                                for t, (shape, dt) in zip(out, want)):
-            raise ValueError(f"{fn}: out must be (weights, ids, lse, prob_sum, counts) of the call's shapes and dtypes")
-        _dev_check(logits, *out)
+    want = (((T, K), torch.float32), ((T, K), ids_dtype), ((T,), torch.float32), ((E,), torch.float32) if stats else None,
+            ((E,), torch.int64) if stats else None)
+    out = _gate_outputs(fn, logits, want, out, "weights, ids, lse, prob_sum, counts")
     weights, ids, lse = out[:3]
     prob_sum, counts = out[3:] if stats else (None, None)
-    scratch = None
-    sb = 0
     lib = native.hip()
     dt = int(dtype_of_torch(logits.dtype))
-    if stats:
-        sb = lib.mp4x_moe_gate_scratch_bytes(dt, T, E)
-        scratch = torch.empty(max(sb, 1), dtype=torch.uint8, device=dev)
+    scratch, sb = _gate_scratch(lib.mp4x_moe_gate_scratch_bytes, dt, T, E, stats, logits.device)
     if T == 0 and not stats:
         return weights, ids, lse, None, None
     check(lib.mp4x_moe_gate_topk(dt, logits.data_ptr() if T else None, T, E, K, int(bool(renormalize)),
@@ -783,55 +828,45 @@ def moe_gate_backward(logits: torch.Tensor, lse: torch.Tensor, ids: torch.Tensor
     """K10's backward: the gradient of ``logits`` (their dtype, one rounding) from the saved
     ``logits``, ``lse`` and ``ids`` of :func:`moe_gate_topk` and the gradients of ``weights`` [T, K],
     ``lse`` [T] and ``prob_sum`` [E], all float32, each None for zeros."""
-    fn = "moe_gate_backward"
-    _dev_check(logits, lse, ids, g_weights, g_lse, g_prob_sum, out)
-    if ids.dim() != 2 or ids.dtype not in (torch.int32, torch.int64):
-        raise ValueError(f"{fn}: ids must be [T, K] in int32 or int64")
-    T, E, K = _gate_shape(fn, logits, int(ids.shape[1]))
-    if ids.shape[0] != T:
-        raise ValueError(f"{fn}: {ids.shape[0]} rows of ids for {T} rows of logits")
-    for name, t, shape in (("lse", lse, (T,)), ("g_weights", g_weights, (T, K)), ("g_lse", g_lse, (T,)),
-                           ("g_prob_sum", g_prob_sum, (E,))):
-        if t is not None and (t.dtype != torch.float32 or tuple(t.shape) != shape):
-            raise ValueError(f"{fn}: {name} must be float32 {list(shape)}")
-    if lse is None:
-        raise ValueError(f"{fn}: lse is missing")
-    if out is None:
-        out = torch.empty_like(logits)
-    elif out.dtype != logits.dtype or out.shape != logits.shape:
-        raise ValueError(f"{fn}: out dtype / shape differ from the logits'")
-    if T == 0:
-        return out
-
-    def ptr(t):
-        return t.data_ptr() if t is not None else None
-    check(native.hip().mp4x_moe_gate_backward(int(dtype_of_torch(logits.dtype)), logits.data_ptr(), lse.data_ptr(),
-                                              ids.data_ptr(), int(ids.dtype == torch.int64), T, E, K,
-                                              int(bool(renormalize)), ptr(g_weights), ptr(g_lse), ptr(g_prob_sum),
-                                              out.data_ptr(), stream_ptr(stream)), "mp4x_moe_gate_backward")
-    return out
+    return _gate_backward(
+        "moe_gate_backward", logits, lse, ids, False, g_weights, g_lse, g_prob_sum, out,
+        lambda head, tail: check(native.hip().mp4x_moe_gate_backward(*head, int(bool(renormalize)), *tail, stream_ptr(stream)),
+                                 "mp4x_moe_gate_backward"))
 
 
 MOE_GATE_MAX_GROUPS = 32
 MOE_GATE_SCORES = ("softmax", "sigmoid")          # the C ABI's score argument is the index
 
 
-def _gate_group_args(fn: str, E: int, K: int, score, n_group, topk_group, scale) -> Tuple[int, int, int, float]:
-    """(score index, n_group, topk_group, scale) of a K13 call, checked as csrc/kernels/moe_gate_group.hip
-    checks them."""
+def gate_group_args(where: str, E: int, K: int, score, n_group, topk_group, scale, max_groups: Optional[int] = None,
+                    names=("n_group", "topk_group", "scale", "E")) -> Tuple[int, int, float]:
+    """``(n_group, topk_group, scale)`` of the group-limited gate over E experts with top K, checked
+    (``topk_group`` None is ``n_group``): the one check behind ``route_topk_grouped``, the layer's
+    constructor and the K13 wrappers.  ``where`` opens the message and ``names`` are the caller's names
+    of its arguments; ``max_groups`` is the kernel's limit, None where there is none.  Loads nothing."""
+    gn, kn, sn, en = names
     if score not in MOE_GATE_SCORES:
-        raise ValueError(f"{fn}: score {score!r} is not 'softmax' or 'sigmoid'")
-    if isinstance(n_group, bool) or not isinstance(n_group, int) or not 1 <= n_group <= MOE_GATE_MAX_GROUPS or E % n_group:
-        raise ValueError(f"{fn}: n_group {n_group!r} is not an int in [1, {MOE_GATE_MAX_GROUPS}] that divides E = {E}")
+        raise ValueError(f"{where}score {score!r} is not 'softmax' or 'sigmoid'")
+    if (isinstance(n_group, bool) or not isinstance(n_group, int) or n_group < 1 or E % n_group
+            or (max_groups is not None and n_group > max_groups)):
+        what = "a positive int" if max_groups is None else f"an int in [1, {max_groups}]"
+        raise ValueError(f"{where}{gn} {n_group!r} is not {what} that divides {en} = {E}")
     if topk_group is None:
         topk_group = n_group
     if isinstance(topk_group, bool) or not isinstance(topk_group, int) or not 1 <= topk_group <= n_group:
-        raise ValueError(f"{fn}: topk_group {topk_group!r} is not an int in [1, n_group = {n_group}]")
+        raise ValueError(f"{where}{kn} {topk_group!r} is not an int in [1, {gn} = {n_group}]")
     if K > topk_group * (E // n_group):
-        raise ValueError(f"{fn}: top_k {K} is more than the {topk_group} x {E // n_group} experts of the chosen groups")
+        raise ValueError(f"{where}top_k {K} is more than the {topk_group} x {E // n_group} experts of the chosen groups")
     scale = float(scale)
     if not (scale > 0.0 and scale != float("inf")):
-        raise ValueError(f"{fn}: scale {scale!r} is not finite and positive")
+        raise ValueError(f"{where}{sn} {scale!r} is not finite and positive")
+    return n_group, topk_group, scale
+
+
+def _gate_group_args(fn: str, E: int, K: int, score, n_group, topk_group, scale) -> Tuple[int, int, int, float]:
+    """(score index, n_group, topk_group, scale) of a K13 call, checked as csrc/kernels/moe_gate_group.hip
+    checks them."""
+    n_group, topk_group, scale = gate_group_args(f"{fn}: ", E, K, score, n_group, topk_group, scale, MOE_GATE_MAX_GROUPS)
     return MOE_GATE_SCORES.index(score), n_group, topk_group, scale
 
 
@@ -855,35 +890,20 @@ def moe_gate_group_topk(logits: torch.Tensor, top_k: int, score: str = "sigmoid"
         raise ValueError(f"{fn}: ids_dtype must be int32 or int64")
     if bias is not None and (bias.dtype != torch.float32 or tuple(bias.shape) != (E,) or not bias.is_contiguous()):
         raise ValueError(f"{fn}: bias must be contiguous float32 [{E}]")
-    dev = logits.device
     want = (((T, K), torch.float32), ((T, K), ids_dtype), ((T,), torch.float32) if sc == 0 else None,
             ((E,), torch.float32) if stats else None, ((E,), torch.int64) if stats else None, ((T, Kg), torch.int32))
-    if out is None:
-        out = tuple(None if w is None else torch.empty(w[0], dtype=w[1], device=dev) for w in want)
-    else:
-        out = tuple(out)
-        if len(out) != 6 or any((t is not None) if w is None else (not isinstance(t, torch.Tensor) or tuple(t.shape) != w[0]
-                                                                    or t.dtype != w[1] or not t.is_contiguous())
-                                for t, w in zip(out, want)):
-            raise ValueError(f"{fn}: out must be (weights, ids, lse, prob_sum, counts, group_ids) of the call's shapes "
-                             "and dtypes, None where the call has none")
-        _dev_check(logits, *out)
+    out = _gate_outputs(fn, logits, want, out, "weights, ids, lse, prob_sum, counts, group_ids")
+    if any(w is None and t is not None for t, w in zip(out, want)):
+        raise ValueError(f"{fn}: out must be None where the call has none")
     weights, ids, lse, prob_sum, counts, group_ids = out
-    scratch = None
-    sb = 0
     lib = native.hip()
     dt = int(dtype_of_torch(logits.dtype))
-    if stats:
-        sb = lib.mp4x_moe_gate_group_scratch_bytes(dt, T, E)
-        scratch = torch.empty(max(sb, 1), dtype=torch.uint8, device=dev)
+    scratch, sb = _gate_scratch(lib.mp4x_moe_gate_group_scratch_bytes, dt, T, E, stats, logits.device)
     if T == 0 and not stats:
         return out
-
-    def ptr(t):
-        return t.data_ptr() if (t is not None and T) else None
-    check(lib.mp4x_moe_gate_group_topk(dt, ptr(logits), bias.data_ptr() if bias is not None else None, T, E, K, Gr, Kg, sc,
-                                       int(bool(renormalize)), scale, ptr(weights), ptr(ids),
-                                       int(ids_dtype == torch.int64), ptr(group_ids), ptr(lse),
+    check(lib.mp4x_moe_gate_group_topk(dt, _ptr(logits, T), bias.data_ptr() if bias is not None else None, T, E, K, Gr, Kg, sc,
+                                       int(bool(renormalize)), scale, _ptr(weights, T), _ptr(ids, T),
+                                       int(ids_dtype == torch.int64), _ptr(group_ids, T), _ptr(lse, T),
                                        prob_sum.data_ptr() if stats else None, counts.data_ptr() if stats else None,
                                        scratch.data_ptr() if stats else None, sb, stream_ptr(stream)),
           "mp4x_moe_gate_group_topk")
@@ -899,36 +919,11 @@ def moe_gate_group_backward(logits: torch.Tensor, lse: Optional[torch.Tensor], i
     ``weights`` [T, K], ``lse`` [T] and ``prob_sum`` [E], all float32, each None for zeros.  The
     sigmoid score has no ``lse``: ``lse`` and ``g_lse`` must be None."""
     fn = "moe_gate_group_backward"
-    _dev_check(logits, lse, ids, g_weights, g_lse, g_prob_sum, out)
-    if ids.dim() != 2 or ids.dtype not in (torch.int32, torch.int64):
-        raise ValueError(f"{fn}: ids must be [T, K] in int32 or int64")
-    T, E, K = _gate_shape(fn, logits, int(ids.shape[1]))
-    sc, _, _, scale = _gate_group_args(fn, E, K, score, 1, 1, scale)
-    if ids.shape[0] != T:
-        raise ValueError(f"{fn}: {ids.shape[0]} rows of ids for {T} rows of logits")
-    for name, t, shape in (("lse", lse, (T,)), ("g_weights", g_weights, (T, K)), ("g_lse", g_lse, (T,)),
-                           ("g_prob_sum", g_prob_sum, (E,))):
-        if t is not None and (t.dtype != torch.float32 or tuple(t.shape) != shape):
-            raise ValueError(f"{fn}: {name} must be float32 {list(shape)}")
-    if sc == 0 and lse is None:
-        raise ValueError(f"{fn}: lse is missing")
-    if sc == 1 and (lse is not None or g_lse is not None):
-        raise ValueError(f"{fn}: the sigmoid score has no lse")
-    if out is None:
-        out = torch.empty_like(logits)
-    elif out.dtype != logits.dtype or out.shape != logits.shape:
-        raise ValueError(f"{fn}: out dtype / shape differ from the logits'")
-    if T == 0:
-        return out
-
-    def ptr(t):
-        return t.data_ptr() if t is not None else None
-    check(native.hip().mp4x_moe_gate_group_backward(int(dtype_of_torch(logits.dtype)), logits.data_ptr(), ptr(lse),
-                                                    ids.data_ptr(), int(ids.dtype == torch.int64), T, E, K, sc,
-                                                    int(bool(renormalize)), scale, ptr(g_weights), ptr(g_lse),
-                                                    ptr(g_prob_sum), out.data_ptr(), stream_ptr(stream)),
-          "mp4x_moe_gate_group_backward")
-    return out
+    sc, _, _, scale = _gate_group_args(fn, 1, 1, score, 1, 1, scale)      # one group of one expert: the score and the scale
+    return _gate_backward(
+        fn, logits, lse, ids, sc == 1, g_weights, g_lse, g_prob_sum, out,
+        lambda head, tail: check(native.hip().mp4x_moe_gate_group_backward(*head, sc, int(bool(renormalize)), scale, *tail,
+                                                                           stream_ptr(stream)), "mp4x_moe_gate_group_backward"))
 
 
 # int64 key sorts: rocPRIM's own dispatch (block sort + merge passes below 1 M items, whatever the

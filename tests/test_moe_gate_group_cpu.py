@@ -2,14 +2,16 @@
 and its closed-form backward) against the float64 definition of tests/moe_gate_group_ref.py: scores,
 weights, lse, prob_sum and the gradient inside the derived bounds (DESIGN "K13"), the selection by
 the tolerance-aware check everywhere and exactly on the separated fixtures, which are asserted to be
-separated; without a bias and with one group the ids are ``gate_forward_torch``'s."""
+separated; without a bias and with one group the ids are the plain gate's definition's
+(tests/moe_gate_ref.py) and the softmax score gives ``route_topk``'s bits."""
 import pytest
 
 torch = pytest.importorskip("torch")
 
 import moe_gate_group_ref as ref  # noqa: E402
 import moe_gate_ref  # noqa: E402
-from mp4x.models.moe import (gate_forward_torch, gate_group_backward_torch, gate_group_forward_torch,  # noqa: E402
+from moe_ref import same_bits  # noqa: E402
+from mp4x.models.moe import (gate_group_backward_torch, gate_group_forward_torch, route_topk,  # noqa: E402
                              route_topk_grouped)
 
 T = 65
@@ -127,16 +129,28 @@ def test_no_bias_and_one_group_give_the_ids_of_the_plain_gate(dtype):
     dt = getattr(torch, dtype)
     for E in (1, 2, 5, 64, 257):
         for K in sorted({min(k, E) for k in (1, 2, 8, 16)}):
-            logits = moe_gate_ref.tie_logits(T, E, 500 + E, dt)
-            want = gate_forward_torch(logits, K, True, torch.int64, False)
+            # the float64 definition of the plain gate (tests/moe_gate_ref.py), not the code under test
+            logits, want = moe_gate_ref.cached_reference("ties", T, E, K, True, 0, 500 + E, dtype)
             for score in ("softmax", "sigmoid"):
                 res = route_topk_grouped(logits, K, score=score, renormalize=True)
-                assert torch.equal(res.ids, want[1]), (E, K, score)
+                assert torch.equal(res.ids, moe_gate_ref.order_ids(logits, K)), (E, K, score)
                 assert bool((res.group_ids == 0).all()) and res.group_ids.shape == (T, 1)
-            # the softmax score with nothing else is the plain gate, bit for bit
-            res = route_topk_grouped(logits, K, score="softmax", renormalize=True)
-            assert moe_gate_ref.inside(res.weights, want[0].double(), torch.zeros_like(want[0]).double())[0]
-            assert moe_gate_ref.inside(res.lse, want[2].double(), torch.zeros_like(want[2]).double())[0]
+            # the softmax score with nothing else is the plain gate: inside the plain gate's own bounds ...
+            lg = logits.clone().requires_grad_(True)
+            res = route_topk_grouped(lg, K, score="softmax", renormalize=True, stats=True)
+            assert moe_gate_ref.inside(res.weights, want.w, want.weights_bound())[0], (E, K, "weights")
+            assert moe_gate_ref.inside(res.lse, want.lse, want.lse_bound())[0], (E, K, "lse")
+            # ... and route_topk bit for bit, forward and backward of the same scalar
+            lp = logits.clone().requires_grad_(True)
+            plain = route_topk(lp, K, True, stats=True)
+            assert same_bits(res.weights, plain.weights) and same_bits(res.lse, plain.lse), (E, K)
+            assert same_bits(res.prob_sum, plain.prob_sum), (E, K, "prob_sum")
+            assert torch.equal(res.ids, plain.ids) and torch.equal(res.counts, plain.counts), (E, K)
+            grads = moe_gate_ref.gradients(T, E, K, 600 + E)
+            for r, leaf in ((res, lg), (plain, lp)):
+                ((r.weights * grads[0]).sum() + (r.lse * grads[1]).sum() + (r.prob_sum * grads[2]).sum()).backward()
+                assert leaf.grad.dtype == dt
+            assert same_bits(lg.grad, lp.grad), (E, K, "logits.grad")
     nan, inf = float("nan"), float("inf")
     for E, K, Gr, Kg in ((5, 5, 1, 1), (64, 8, 1, 1), (257, 16, 1, 1), (64, 8, 8, 4), (2048, 16, 32, 8)):
         lg = moe_gate_ref.uniform_logits(9, E, 4, 77)
@@ -153,9 +167,10 @@ def test_no_bias_and_one_group_give_the_ids_of_the_plain_gate(dtype):
             assert bool(((gids >= 0) & (gids < Gr)).all()) and all(len(set(r)) == Kg for r in gids.tolist())
             assert bool(((ids // (E // Gr)).unsqueeze(2) == gids.unsqueeze(1)).any(dim=-1).all())
             if Gr == 1 and bias is None:
-                # every row, the NaN and infinite ones included, as the plain gate's torch form orders it
-                # (both sort the logits with the same stable sort); the ordinary rows as the definition
-                assert torch.equal(ids, gate_forward_torch(lg.to(dt), K, True, torch.int64, False)[1])
+                # every row, the NaN and infinite ones included, as a stable descending sort of the
+                # float32 logits orders it; the ordinary rows as the definition
+                order = torch.sort(lg.to(dt).to(torch.float32), dim=-1, descending=True, stable=True).indices[:, :K]
+                assert torch.equal(ids, order)
                 assert torch.equal(ids[7:], moe_gate_ref.order_ids(lg.to(dt)[7:], K))
 
 

@@ -144,14 +144,23 @@ def test_no_bias_and_one_group_give_the_ids_of_k10(dtype):
         for n, K in enumerate(sorted({min(k, E) for k in (1, 2, 8, 16)})):
             logits, want = moe_gate_ref.cached_reference("ties", 65, E, K, True, 0, 500 + E, dtype)
             ld = logits.to(DEV)
-            k10 = ops.moe_gate_topk(ld, K, True)
+            k10 = ops.moe_gate_topk(ld, K, True, stats=True)
             for score in ("softmax", "sigmoid"):
                 got = ops.moe_gate_group_topk(ld, K, score, renormalize=True)
                 assert torch.equal(got[1].cpu(), want.ids) and torch.equal(got[1], k10[1]), (E, K, score)
                 assert bool((got[5] == 0).all())
-            # the softmax score with nothing else is K10, bit for bit
-            got = ops.moe_gate_group_topk(ld, K, "softmax", renormalize=True)
+            # the softmax score with nothing else is K10, bit for bit: the forward with its statistics ...
+            got = ops.moe_gate_group_topk(ld, K, "softmax", renormalize=True, stats=True)
             assert same_bits(got[0].cpu(), k10[0].cpu()) and same_bits(got[2].cpu(), k10[2].cpu()), (E, K)
+            assert same_bits(got[3].cpu(), k10[3].cpu()) and torch.equal(got[4], k10[4]), (E, K, "statistics")
+            # ... and the backward of the same (logits, lse, ids) through either entry
+            grads = moe_gate_ref.gradients(65, E, K, 600 + E)
+            for renormalize in (False, True):
+                for which in ((1, 1, 1), (1, 0, 0)):
+                    gd = [None if g is None else g.to(DEV) for g in moe_gate_ref.pick(grads, which)]
+                    g10 = ops.moe_gate_backward(ld, k10[2], k10[1], renormalize, *gd)
+                    g13 = ops.moe_gate_group_backward(ld, k10[2], k10[1], "softmax", renormalize, 1.0, *gd)
+                    assert same_bits(g13.cpu(), g10.cpu()), (E, K, renormalize, which)
 
 
 def test_any_bits_give_ids_in_range_distinct_and_inside_the_chosen_groups():
