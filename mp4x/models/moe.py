@@ -36,6 +36,7 @@ import torch
 
 from ..operands import Operands
 from ..operators import Operators
+from ..parallel.moe import combine_weight_grad_torch
 
 
 class _Dispatch(torch.autograd.Function):
@@ -72,14 +73,7 @@ class _Combine(torch.autograd.Function):
                                                     row_scale=weights)
         g_w = None
         if weights is not None and ctx.needs_input_grad[1]:
-            T, K = plan.num_tokens, plan.top_k
-            sl = plan.slots.view(T, K)
-            if back.shape[0] and T:          # (a padded plan has rows even for a rank with no token)
-                y = back.reshape(back.shape[0], -1)[sl.clamp(min=0)].to(torch.float32)      # [T, K, H]
-                g_w = (g.reshape(T, 1, -1).to(torch.float32) * y).sum(-1)
-                g_w = torch.where(sl >= 0, g_w, torch.zeros_like(g_w)).view_as(weights)
-            else:
-                g_w = torch.zeros_like(weights)
+            g_w = combine_weight_grad_torch(g, plan.slots, back, plan.num_tokens, plan.top_k).view_as(weights)
         return g_rows, g_w, None, None, None, None
 
 

@@ -477,6 +477,21 @@ def moe_route_count(ids: torch.Tensor, nb: int, stream=None) -> RouteCount:
     return RouteCount(ids, nb, counts, scratch)
 
 
+def _moe_scatter_args(fn: str, rc: RouteCount, x: torch.Tensor, top_k: int, out_rows: torch.Tensor,
+                      row_scale: Optional[torch.Tensor]) -> Tuple[int, int]:
+    """What both K9 scatters ask of their arguments; (assignments, bytes of a row)."""
+    n = rc.ids.numel()
+    _dev_check(rc.ids, x, out_rows, row_scale)
+    _, rb = _moe_rows(fn, x)
+    if top_k < 1 or x.shape[0] * top_k != n:
+        raise ValueError(f"{fn}: {x.shape[0]} rows x top_k {top_k} != {n} ids")
+    if out_rows.dtype != x.dtype or tuple(out_rows.shape[1:]) != tuple(x.shape[1:]):
+        raise ValueError(f"{fn}: out_rows dtype / row shape differ from x")
+    if row_scale is not None and (row_scale.dtype != torch.float32 or row_scale.numel() != n):
+        raise ValueError(f"{fn}: row_scale must be float32, one per assignment")
+    return n, rb
+
+
 def moe_route_scatter(rc: RouteCount, x: torch.Tensor, top_k: int, out_rows: torch.Tensor,
                       row_scale: Optional[torch.Tensor] = None, placed: Optional[int] = None,
                       stream=None, clip: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -490,15 +505,7 @@ def moe_route_scatter(rc: RouteCount, x: torch.Tensor, top_k: int, out_rows: tor
     ``prefix[e] + pe``; the others get -1 and their rows are neither read nor written.  ``out_rows``
     must then hold ``keep.sum()`` rows, which the caller gives as ``placed`` (no sync here)."""
     ids = rc.ids
-    n = ids.numel()
-    _dev_check(ids, x, out_rows, row_scale)
-    _, rb = _moe_rows("moe_route_scatter", x)
-    if top_k < 1 or x.shape[0] * top_k != n:
-        raise ValueError(f"moe_route_scatter: {x.shape[0]} rows x top_k {top_k} != {n} ids")
-    if out_rows.dtype != x.dtype or tuple(out_rows.shape[1:]) != tuple(x.shape[1:]):
-        raise ValueError("moe_route_scatter: out_rows dtype / row shape differ from x")
-    if row_scale is not None and (row_scale.dtype != torch.float32 or row_scale.numel() != n):
-        raise ValueError("moe_route_scatter: row_scale must be float32, one per assignment")
+    n, rb = _moe_scatter_args("moe_route_scatter", rc, x, top_k, out_rows, row_scale)
     if clip is not None:
         _dev_check(ids, clip)
         if clip.dtype != torch.int64 or tuple(clip.shape) != (2 * rc.nb,) or not clip.is_contiguous():
@@ -526,6 +533,23 @@ def moe_route_scatter(rc: RouteCount, x: torch.Tensor, top_k: int, out_rows: tor
     return slots
 
 
+def _moe_combine_args(fn: str, rows: torch.Tensor, slots: torch.Tensor, weights: Optional[torch.Tensor],
+                      num_tokens: int, top_k: int, out: Optional[torch.Tensor]):
+    """What both K9 combines ask of their rows, slots, weights and ``out`` (``[num_tokens, ...]`` in the
+    rows' dtype; None: made here); (elements of a row, assignments, out)."""
+    width, _ = _moe_rows(fn, rows)
+    n = num_tokens * top_k
+    if slots.dtype != torch.int64 or slots.numel() != n or top_k < 1:
+        raise ValueError(f"{fn}: slots must be int64, num_tokens * top_k of them")
+    if weights is not None and (weights.dtype != torch.float32 or weights.numel() != n):
+        raise ValueError(f"{fn}: weights must be float32, one per assignment")
+    if out is None:
+        out = torch.empty((num_tokens,) + tuple(rows.shape[1:]), dtype=rows.dtype, device=rows.device)
+    elif out.dtype != rows.dtype or tuple(out.shape) != (num_tokens,) + tuple(rows.shape[1:]):
+        raise ValueError(f"{fn}: out dtype / shape mismatch")
+    return width, n, out
+
+
 def moe_combine(rows: torch.Tensor, slots: torch.Tensor, weights: Optional[torch.Tensor], num_tokens: int,
                 top_k: int, out: Optional[torch.Tensor] = None, max_slot: Optional[int] = None, stream=None):
     """K9's combine: ``out[t] = sum over k, in k order, of weights[t, k] * rows[slots[t * top_k + k]]``
@@ -533,16 +557,7 @@ def moe_combine(rows: torch.Tensor, slots: torch.Tensor, weights: Optional[torch
     ``rows.dtype``).  ``max_slot`` is the largest slot when the caller already knows it (the plan's
     send total - 1); otherwise it is read back from ``slots`` for the bounds check."""
     _dev_check(rows, slots, weights, out)
-    width, _ = _moe_rows("moe_combine", rows)
-    n = num_tokens * top_k
-    if slots.dtype != torch.int64 or slots.numel() != n or top_k < 1:
-        raise ValueError("moe_combine: slots must be int64, num_tokens * top_k of them")
-    if weights is not None and (weights.dtype != torch.float32 or weights.numel() != n):
-        raise ValueError("moe_combine: weights must be float32, one per assignment")
-    if out is None:
-        out = torch.empty((num_tokens,) + tuple(rows.shape[1:]), dtype=rows.dtype, device=rows.device)
-    elif out.dtype != rows.dtype or tuple(out.shape) != (num_tokens,) + tuple(rows.shape[1:]):
-        raise ValueError("moe_combine: out dtype / shape mismatch")
+    width, n, out = _moe_combine_args("moe_combine", rows, slots, weights, num_tokens, top_k, out)
     if n == 0:
         return out
     if max_slot is None:
@@ -572,18 +587,10 @@ def moe_route_scatter_pad(rc: RouteCount, x: torch.Tensor, top_k: int, out_rows:
     every other row of ``out_rows`` is written as zeros, each row exactly once.  Every shape is
     known before the ids are: nothing is read back, nothing is copied to the device."""
     ids = rc.ids
-    n = ids.numel()
-    _dev_check(ids, x, out_rows, row_scale)
-    _, rb = _moe_rows("moe_route_scatter_pad", x)
     cap = _moe_share("moe_route_scatter_pad", rc.nb, cap)
-    if top_k < 1 or x.shape[0] * top_k != n:
-        raise ValueError(f"moe_route_scatter_pad: {x.shape[0]} rows x top_k {top_k} != {n} ids")
-    if out_rows.dtype != x.dtype or tuple(out_rows.shape[1:]) != tuple(x.shape[1:]):
-        raise ValueError("moe_route_scatter_pad: out_rows dtype / row shape differ from x")
+    n, rb = _moe_scatter_args("moe_route_scatter_pad", rc, x, top_k, out_rows, row_scale)
     if out_rows.shape[0] != rc.nb * cap:
         raise ValueError(f"moe_route_scatter_pad: out_rows holds {out_rows.shape[0]} rows, not {rc.nb} x {cap}")
-    if row_scale is not None and (row_scale.dtype != torch.float32 or row_scale.numel() != n):
-        raise ValueError("moe_route_scatter_pad: row_scale must be float32, one per assignment")
     slots = torch.empty(n, dtype=torch.int64, device=ids.device)
     check(native.hip().mp4x_moe_route_scatter_pad(
         int(dtype_of_torch(x.dtype)), ids.data_ptr() if n else None, int(ids.dtype == torch.int64),
@@ -625,18 +632,9 @@ def moe_combine_rows(rows: torch.Tensor, slots: torch.Tensor, weights: Optional[
     that made them bounds them by ``rows.shape[0]`` = nb * cap by construction), so nothing is read
     back for a bounds check.  Rows no slot names are never read."""
     _dev_check(rows, slots, weights, out)
-    width, _ = _moe_rows("moe_combine_rows", rows)
-    n = num_tokens * top_k
-    if slots.dtype != torch.int64 or slots.numel() != n or top_k < 1:
-        raise ValueError("moe_combine_rows: slots must be int64, num_tokens * top_k of them")
-    if weights is not None and (weights.dtype != torch.float32 or weights.numel() != n):
-        raise ValueError("moe_combine_rows: weights must be float32, one per assignment")
+    width, n, out = _moe_combine_args("moe_combine_rows", rows, slots, weights, num_tokens, top_k, out)
     if rows.shape[0] < 1:
         raise ValueError("moe_combine_rows: no rows")
-    if out is None:
-        out = torch.empty((num_tokens,) + tuple(rows.shape[1:]), dtype=rows.dtype, device=rows.device)
-    elif out.dtype != rows.dtype or tuple(out.shape) != (num_tokens,) + tuple(rows.shape[1:]):
-        raise ValueError("moe_combine_rows: out dtype / shape mismatch")
     if n == 0:
         return out
     check(native.hip().mp4x_moe_combine_rows(int(dtype_of_torch(rows.dtype)), rows.data_ptr(), rows.shape[0],
@@ -674,6 +672,7 @@ def moe_combine_backward(g: torch.Tensor, rows: torch.Tensor, slots: torch.Tenso
         raise ValueError(f"{fn}: {num_tokens} tokens x top_k {top_k} is past the routed limit")
     if g.dtype != rows.dtype or tuple(g.shape) != (num_tokens,) + tuple(rows.shape[1:]):
         raise ValueError(f"{fn}: g must be {(num_tokens,) + tuple(rows.shape[1:])} in the rows' dtype")
+    # (K11's own slot and weight checks stay inlined: through _moe_combine_args a 13 us call measured 0.3 us slower)
     if slots.dtype != torch.int64 or slots.numel() != n:
         raise ValueError(f"{fn}: slots must be int64, num_tokens * top_k of them")
     if weights is None or weights.dtype != torch.float32 or weights.numel() != n:

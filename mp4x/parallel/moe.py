@@ -53,12 +53,22 @@ from the output gradient ``g``: the expert rows' is ``g`` dispatched again along
 gate weights as row scale, the weights' the dot of ``g[t]`` with every slot row of token t.  Both
 walk the same slots of buffers of one shape, so one pass does both (K11) and the exchange follows.
 
+The layout of a plan is chosen in one place, :func:`_layout`, from ``source_capacity`` (by ``dispatch``
+for a new plan, by ``TokenPlan`` for one built from keywords); the plan carries it as ``_layout``.  A
+layout (:class:`_Ragged`, with or without a capacity, or :class:`_Padded`) answers what differs: how a
+route becomes send rows and a plan (``route``); the K9 / K11 wrapper and the bound it is given
+(``scatter``, ``combine``, ``combine_backward``); how rows cross ranks and change between source and
+expert order (``exchange``, ``regroup``); the shape of the expert rows a combine takes
+(``check_expert_rows``); whether the send buffer has rows nobody writes (``has_pad_rows``) and whether
+a call may be captured (``capturable``).  Every torch form exists once and asks only ``has_pad_rows``.
+
 GPU tensors run the K9 / K11 kernels (``csrc/kernels/moe.hip``); host tensors, and GPU tensors where
 the native library is absent, run the torch implementation of the same contract below.
 """
 from __future__ import annotations
 
 import math
+from itertools import accumulate
 from typing import List, Optional, Sequence, Tuple
 
 import torch
@@ -95,11 +105,13 @@ class TokenPlan:
     there.  Inside a captured graph every replay rewrites ``slots``, ``kept``, ``valid``, ``dropped``."""
     __slots__ = ("num_tokens", "top_k", "num_experts", "expert_counts", "send_counts", "recv_counts", "slots",
                  "matrix", "expert_matrix", "row_shape", "dtype", "rank", "capacity", "demand_matrix", "clipped",
-                 "source_capacity", "kept", "valid", "dropped", "_route", "_clip", "_frozen")
+                 "source_capacity", "kept", "valid", "dropped", "_route", "_clip", "_layout", "_frozen")
 
     def __init__(self, **kw):
         kw = {"capacity": None, "demand_matrix": kw.get("expert_matrix"), "clipped": 0, "_clip": None,
               "source_capacity": None, "kept": None, "valid": None, "dropped": None, **kw}
+        if "_layout" not in kw:
+            kw["_layout"] = _layout(kw["source_capacity"])
         for k, v in kw.items():
             object.__setattr__(self, k, v)
         object.__setattr__(self, "_frozen", True)
@@ -118,9 +130,7 @@ class TokenPlan:
         slots' device, the running sum of ``expert_counts``."""
         if self.source_capacity is not None:
             return ("padded", self.valid, self.source_capacity)
-        offsets = [0]
-        for c in self.expert_counts:
-            offsets.append(offsets[-1] + int(c))
+        offsets = [0] + list(accumulate(int(c) for c in self.expert_counts))
         return ("ragged", torch.tensor(offsets, dtype=torch.int64).to(self.slots.device))
 
 
@@ -138,7 +148,7 @@ def _width(shape: Sequence[int]) -> int:
     return w
 
 
-def _check_rows(what: str, t: torch.Tensor, padded: bool = False):
+def _check_rows(what: str, t: torch.Tensor, layout):
     if not isinstance(t, torch.Tensor):
         raise Mp4jException(f"{what} needs a torch tensor")
     if t.dim() < 1 or not t.is_contiguous():
@@ -148,7 +158,7 @@ def _check_rows(what: str, t: torch.Tensor, padded: bool = False):
     rb = _width(t.shape[1:]) * t.element_size()
     if rb == 0 or (t.is_cuda and rb % 16):
         raise Mp4jException(f"{what}: rows of {rb} bytes on a GPU tensor are not whole 16-byte vectors")
-    if t.is_cuda and not padded:          # the padded layout exchanges no counts: it may be captured
+    if t.is_cuda and not layout.capturable:       # the padded layout exchanges no counts: it may be captured
         from ..ops.native import capturing_now
         if capturing_now():
             raise Mp4jException(f"{what} inside a graph capture: the count exchange is a host sync")
@@ -169,12 +179,51 @@ def _torch_route(ids: torch.Tensor, nb: int):
     return counts, slots, order
 
 
-def _torch_scatter(x: torch.Tensor, order: torch.Tensor, top_k: int, row_scale: Optional[torch.Tensor]):
-    rows = x[order // top_k]
-    if row_scale is None:
-        return rows
-    s = row_scale.reshape(-1)[order].view((-1,) + (1,) * (x.dim() - 1))
-    return (s * rows.to(torch.float32)).to(x.dtype)
+def _torch_place(route, ids: torch.Tensor, nb: int, limit: torch.Tensor, base: torch.Tensor) -> torch.Tensor:
+    """The slots of ``_torch_route``'s result under a per-expert limit: the ``pe``-th assignment of
+    expert e (its position inside its expert, in assignment order) stays iff ``pe < limit[e]``, at
+    slot ``base[e] + pe``; every other assignment gets -1."""
+    counts, slots, order = route
+    start = torch.cumsum(counts[:nb], 0) - counts[:nb]
+    e = ids.to(torch.int64)[order]
+    pe = torch.arange(order.numel(), dtype=torch.int64, device=ids.device) - start[e]
+    stay = pe < limit[e]
+    slots = torch.full_like(slots, -1)
+    slots[order[stay]] = base[e[stay]] + pe[stay]
+    return slots
+
+
+def _torch_clip(route, ids: torch.Tensor, nb: int, keep: Sequence[int]) -> torch.Tensor:
+    """The ragged slots under the quota ``keep[e]``: the kept assignments close ranks (still the
+    stable sort), expert e's from ``kept_base[e]``, the exclusive prefix of ``keep``."""
+    keep_t = torch.tensor(list(keep), dtype=torch.int64, device=ids.device)
+    return _torch_place(route, ids, nb, keep_t, torch.cumsum(keep_t, 0) - keep_t)
+
+
+def _torch_pad(route, ids: torch.Tensor, nb: int, S: int):
+    """The torch form of the padded route: (slots int64[n], kept int64[nb], dropped int64[3]); expert
+    e keeps its first S assignments, from slot ``e*S``."""
+    counts = route[0]
+    e = torch.arange(nb, dtype=torch.int64, device=ids.device)
+    slots = _torch_place(route, ids, nb, torch.full_like(e, S), e * S)
+    kept = counts[:nb].clamp(max=S)
+    dropped = torch.stack([(counts[:nb] - kept).sum(), counts[nb], counts[nb + 1]])
+    return slots, kept, dropped
+
+
+def _torch_scatter(x: torch.Tensor, slots: torch.Tensor, top_k: int, row_scale: Optional[torch.Tensor],
+                   out: torch.Tensor, has_pad_rows: bool) -> torch.Tensor:
+    """``out[slots[a]] = x[a // K]`` (times ``row_scale[a]``, one rounding) for ``slots[a] >= 0``; the
+    rows no slot names, which only a layout with pad rows has, are zeros."""
+    if has_pad_rows:
+        out.zero_()
+    a = torch.nonzero(slots >= 0).reshape(-1)
+    rows = x[a // top_k]
+    if row_scale is not None:
+        s = row_scale.reshape(-1)[a].view((-1,) + (1,) * (x.dim() - 1))
+        rows = (s * rows.to(torch.float32)).to(x.dtype)
+    out[slots[a]] = rows
+    return out
 
 
 def _torch_combine(rows: torch.Tensor, slots: torch.Tensor, weights: Optional[torch.Tensor], T: int, K: int):
@@ -192,18 +241,15 @@ def _torch_combine(rows: torch.Tensor, slots: torch.Tensor, weights: Optional[to
     return acc.to(rows.dtype)
 
 
-def _torch_clip(route, ids: torch.Tensor, nb: int, keep: Sequence[int]):
-    """``_torch_route``'s result under the quota ``keep[e]``: the assignments past it leave the
-    slots and the order; the others close ranks (still the stable sort)."""
-    counts, slots, order = route
-    keep_t = torch.tensor(list(keep), dtype=torch.int64, device=ids.device)
-    start = torch.cumsum(counts[:nb], 0) - counts[:nb]
-    e = ids.to(torch.int64)[order]
-    pe = torch.arange(order.numel(), dtype=torch.int64, device=ids.device) - start[e]
-    order = order[pe < keep_t[e]]
-    slots = torch.full_like(slots, -1)
-    slots[order] = torch.arange(order.numel(), dtype=torch.int64, device=ids.device)
-    return counts, slots, order
+def combine_weight_grad_torch(g: torch.Tensor, slots: torch.Tensor, slot_rows: torch.Tensor, T: int, K: int):
+    """The combine's gradient w.r.t. its weights in torch, float32 ``[T, K]``: ``g_w[t, k] = g[t] .
+    slot_rows[slots[t, k]]`` in float32, +0 where the slot is negative; zeros without rows or tokens."""
+    if not (slot_rows.shape[0] and T):      # (a padded plan has rows even for a rank with no token)
+        return torch.zeros((T, K), dtype=torch.float32, device=g.device)
+    sl = slots.view(T, K)
+    y = slot_rows.reshape(slot_rows.shape[0], -1)[sl.clamp(min=0)].to(torch.float32)      # [T, K, H]
+    g_w = (g.reshape(T, 1, -1).to(torch.float32) * y).sum(-1)
+    return torch.where(sl >= 0, g_w, torch.zeros_like(g_w))
 
 
 # ---------------------------------------------------------------- expert capacity
@@ -294,26 +340,26 @@ def _exchange(engine, send: torch.Tensor, send_counts, mat, operand):
 
 
 # ---------------------------------------------------------------- dispatch
-def _route_rows(x: torch.Tensor, plan_route, top_k: int, placed: int, row_scale: Optional[torch.Tensor],
-                clip: Optional[torch.Tensor] = None):
-    """Rows of ``x`` replicated into send order (the second half of the route).  ``clip``: the
-    device ``[keep | kept_base]`` of a capped call (the torch form's route is clipped already)."""
+def _scatter(layout, x: torch.Tensor, route, top_k: int, row_scale: Optional[torch.Tensor], send: torch.Tensor,
+             clip: Optional[torch.Tensor] = None):
+    """Rows of ``x`` replicated into ``send`` along ``route`` (the second half of the route, times
+    ``row_scale``); returns the slots.  ``route``: the native ``RouteCount``, in the torch form the slots.
+    ``clip``: the device ``[keep | kept_base]`` of a capped native call (the torch form's slots are clipped
+    already; a padded plan has none)."""
     if _native_ok(x):
-        from ..ops.device_ops import moe_route_scatter
-        out = torch.empty((placed,) + tuple(x.shape[1:]), dtype=x.dtype, device=x.device)
-        slots = moe_route_scatter(plan_route, x, top_k, out, row_scale=row_scale, placed=placed, clip=clip)
-        return out, slots
-    _, slots, order = plan_route
-    return _torch_scatter(x, order, top_k, row_scale), slots
+        return layout.scatter(route, x, top_k, send, row_scale, clip)
+    _torch_scatter(x, route, top_k, row_scale, send, layout.has_pad_rows)
+    return route
 
 
 def dispatch(engine, x: torch.Tensor, expert_ids: torch.Tensor, num_experts: int, operand=None, capacity=None,
              capacity_factor=None, source_capacity=None):
     """``(rows, plan)``: see ``ProcessCommSlave.dispatchTokens``."""
-    p, r = engine.p, engine.rank
+    p = engine.p
     E = int(num_experts)
     _check_source_capacity(source_capacity, capacity, capacity_factor)
-    _check_rows("dispatchTokens", x, padded=source_capacity is not None)
+    layout = _layout(source_capacity)
+    _check_rows("dispatchTokens", x, layout)
     _check_capacity(capacity, capacity_factor)
     if E < 1 or E % p:
         raise Mp4jException(f"dispatchTokens: numExperts {E} is not a positive multiple of the {p} ranks")
@@ -329,77 +375,35 @@ def dispatch(engine, x: torch.Tensor, expert_ids: torch.Tensor, num_experts: int
     if K < 1:
         raise Mp4jException("dispatchTokens: expertIds needs at least one column")
     ids = expert_ids.reshape(-1).contiguous()
-    if source_capacity is not None:
-        return _dispatch_padded(engine, x, ids, T, K, E, source_capacity, operand)
-    native = _native_ok(x)
-    # 1. route count
-    if native:
+    # the first half of the route: K9's histogram + scan, or its torch form
+    if _native_ok(x):
         from ..ops.device_ops import moe_route_count
         route = moe_route_count(ids, E)
-        counts = route.counts
     else:
         route = _torch_route(ids, E)
-        counts = route[0]
-    # 2. the one count exchange: E + 2 numbers per rank
-    if p > 1:
-        from . import sparse
-        rows_ = sparse._count_matrix(engine, counts)
-    else:
-        rows_ = [counts.tolist()]
-    emat = tuple(tuple(int(v) for v in row[:E]) for row in rows_)
-    bad = [(j, int(row[E + 1])) for j, row in enumerate(rows_) if row[E + 1]]
-    if bad:
-        raise Mp4jException(f"dispatchTokens: rank {bad[0][0]} has {bad[0][1]} expert id(s) >= numExperts {E}")
-    # an expert capacity: every rank works out every rank's quota from the demand matrix
-    demand, clip, clipped = emat, None, 0
-    C = _resolve_capacity(capacity, capacity_factor, sum(int(v) for row in rows_ for v in row[:E + 1]), E)
-    if C is not None:
-        emat = capacity_quota(demand, C)
-        keep = emat[r]
-        clipped = sum(demand[r]) - sum(keep)
-        if native:
-            kbase = [0] * E
-            for e in range(1, E):
-                kbase[e] = kbase[e - 1] + keep[e - 1]
-            clip = torch.tensor(list(keep) + kbase, dtype=torch.int64).to(x.device)      # one small H2D copy
-        else:
-            route = _torch_clip(route, ids, E, keep)
-    el = E // p
-    mat = tuple(tuple(sum(emat[i][j * el:(j + 1) * el]) for j in range(p)) for i in range(p))
-    send_counts = mat[r]
-    recv_counts = tuple(mat[i][r] for i in range(p))
-    expert_counts = tuple(sum(emat[i][r * el + e] for i in range(p)) for e in range(el))
-    # 3. route scatter
-    send, slots = _route_rows(x, route, K, sum(send_counts), None, clip)
-    plan = TokenPlan(num_tokens=T, top_k=K, num_experts=E, expert_counts=expert_counts, send_counts=send_counts,
-                     recv_counts=recv_counts, slots=slots, matrix=mat, expert_matrix=emat,
-                     row_shape=tuple(x.shape[1:]), dtype=x.dtype, rank=r, capacity=C, demand_matrix=demand,
-                     clipped=clipped, _route=route, _clip=clip)
-    # 4. the all-to-all with that matrix, 5. expert-major
-    return _forward_rows(engine, send, plan, operand), plan
+    # the layout's: which counts cross ranks, the scatter, the exchange and what the plan says of them
+    got, fields = layout.route(engine, x, ids, route, K, E, operand, capacity, capacity_factor)
+    plan = TokenPlan(num_tokens=T, top_k=K, num_experts=E, row_shape=tuple(x.shape[1:]), dtype=x.dtype,
+                     rank=engine.rank, source_capacity=source_capacity, _layout=layout, **fields)
+    return layout.regroup(got, plan, inverse=False), plan
 
 
-def _forward_rows(engine, send: torch.Tensor, plan: TokenPlan, operand):
-    if len(plan.matrix) == 1:
-        return send                         # one rank: send order is expert-major already
-    got = _exchange(engine, send, plan.send_counts, [list(row) for row in plan.matrix], operand)
-    return _regroup(got, plan, inverse=False)
+def _to_experts(engine, send: torch.Tensor, plan: TokenPlan, operand):
+    """Send order to expert rows: the exchange, then the regroup."""
+    layout = plan._layout
+    return layout.regroup(layout.exchange(engine, send, plan, operand, back=False), plan, inverse=False)
 
 
 def dispatch_scaled(engine, x: torch.Tensor, plan: TokenPlan, row_scale: Optional[torch.Tensor], operand=None):
     """Dispatch ``x`` [T, ...] again along ``plan`` with every assignment's row times
     ``row_scale`` [T, K] (the combine's backward w.r.t. the expert rows): the route scatter with
     the plan's scan, clipping and matrix, no count exchange."""
-    _check_rows("dispatchTokens", x, padded=plan.source_capacity is not None)
+    _check_rows("dispatchTokens", x, plan._layout)
     _check_plan_rows("dispatchTokens", x, plan, plan.num_tokens)
     row_scale = _check_weights(row_scale, plan, x)
-    if plan.source_capacity is not None:
-        send, _, _ = _pad_buffers(x, plan.num_experts, plan.source_capacity, len(plan.matrix), counts=False)
-        _pad_scatter(x, plan._route, plan.top_k, plan.num_experts, plan.source_capacity, row_scale, send)
-        got, _ = _pad_exchange(engine, send, None, None, operand)
-        return _pad_regroup(got, plan, inverse=False)
-    send, _ = _route_rows(x, plan._route, plan.top_k, sum(plan.send_counts), row_scale, plan._clip)
-    return _forward_rows(engine, send, plan, operand)
+    send = torch.empty((sum(plan.send_counts),) + plan.row_shape, dtype=x.dtype, device=x.device)
+    _scatter(plan._layout, x, plan._route, plan.top_k, row_scale, send, plan._clip)
+    return _to_experts(engine, send, plan, operand)
 
 
 # ---------------------------------------------------------------- combine
@@ -424,39 +428,19 @@ def _check_weights(weights, plan: TokenPlan, like: torch.Tensor):
     return weights.contiguous()
 
 
-def return_rows(engine, expert_rows: torch.Tensor, plan: TokenPlan, operand=None) -> torch.Tensor:
-    """Expert rows back on their senders, in the sender's slot order."""
-    if len(plan.matrix) == 1:
-        return expert_rows
-    back = _regroup(expert_rows, plan, inverse=True)
-    p = len(plan.matrix)
-    mat_t = [[plan.matrix[j][i] for j in range(p)] for i in range(p)]
-    return _exchange(engine, back, plan.recv_counts, mat_t, operand)
-
-
-def combine_local(back: torch.Tensor, plan: TokenPlan, weights: Optional[torch.Tensor]) -> torch.Tensor:
-    T, K = plan.num_tokens, plan.top_k
-    if _native_ok(back):
-        from ..ops.device_ops import moe_combine
-        return moe_combine(back, plan.slots, weights, T, K, max_slot=sum(plan.send_counts) - 1)
-    return _torch_combine(back, plan.slots, weights, T, K)
-
-
 def combine(engine, expert_rows: torch.Tensor, plan: TokenPlan, weights=None, operand=None, return_slot_rows=False):
     """``out`` [T, ...]: see ``ProcessCommSlave.combineTokens``."""
     if not isinstance(plan, TokenPlan):
         raise Mp4jException("combineTokens: plan must be the TokenPlan dispatchTokens returned")
-    if plan.source_capacity is not None:
-        return _combine_padded(engine, expert_rows, plan, weights, operand, return_slot_rows)
-    _check_rows("combineTokens", expert_rows)
-    if expert_rows.dim() >= 2 and tuple(expert_rows.shape[2:]) == plan.row_shape and \
-            tuple(expert_rows.shape[1:]) != plan.row_shape:
-        raise Mp4jException(f"combineTokens: rows {tuple(expert_rows.shape)} are in the padded [experts, rows, ...] "
-                            f"layout, the plan is a ragged one (no sourceCapacity)")
-    _check_plan_rows("combineTokens", expert_rows, plan, plan.num_rows)
+    layout = plan._layout
+    layout.check_expert_rows(expert_rows, plan)
     weights = _check_weights(weights, plan, expert_rows)
-    back = return_rows(engine, expert_rows, plan, operand)
-    out = combine_local(back, plan, weights)
+    # expert rows back on their senders, in the sender's slot order: the inverse regroup, then the exchange
+    back = layout.exchange(engine, layout.regroup(expert_rows, plan, inverse=True), plan, operand, back=True)
+    if _native_ok(back):
+        out = layout.combine(back, plan, weights)
+    else:
+        out = _torch_combine(back, plan.slots, weights, plan.num_tokens, plan.top_k)
     return (out, back) if return_slot_rows else out
 
 
@@ -466,23 +450,8 @@ COMBINE_BWD_MAX_TOP_K = 16      # csrc/kernels/moe.hip: kMoeBwdMaxK; a larger K 
 
 def _torch_combine_backward(g: torch.Tensor, plan: TokenPlan, weights: torch.Tensor, slot_rows: torch.Tensor):
     """The torch form of K11's contract: (the gradient rows in slot order, g_weights float32 [T, K])."""
-    T, K = plan.num_tokens, plan.top_k
-    slots = plan.slots
-    if plan.source_capacity is not None:
-        send = _torch_pad_scatter(g, slots, K, weights, torch.empty_like(slot_rows))
-    else:
-        a = torch.nonzero(slots >= 0).reshape(-1)
-        order = torch.empty_like(a)
-        order[slots[a]] = a                  # the placed assignments in slot order
-        send = _torch_scatter(g, order, K, weights)
-    sl = slots.view(T, K)
-    if slot_rows.shape[0] and T:
-        y = slot_rows.reshape(slot_rows.shape[0], -1)[sl.clamp(min=0)].to(torch.float32)      # [T, K, H]
-        g_w = (g.reshape(T, 1, -1).to(torch.float32) * y).sum(-1)
-        g_w = torch.where(sl >= 0, g_w, torch.zeros_like(g_w))
-    else:
-        g_w = torch.zeros((T, K), dtype=torch.float32, device=g.device)
-    return send, g_w
+    send = _torch_scatter(g, plan.slots, plan.top_k, weights, torch.empty_like(slot_rows), plan._layout.has_pad_rows)
+    return send, combine_weight_grad_torch(g, plan.slots, slot_rows, plan.num_tokens, plan.top_k)
 
 
 def combine_backward(engine, g: torch.Tensor, plan: TokenPlan, weights: torch.Tensor, slot_rows: torch.Tensor,
@@ -491,32 +460,19 @@ def combine_backward(engine, g: torch.Tensor, plan: TokenPlan, weights: torch.Te
     what = "combineTokensBackward"
     if not isinstance(plan, TokenPlan):
         raise Mp4jException(f"{what}: plan must be the TokenPlan dispatchTokens returned")
-    padded = plan.source_capacity is not None
-    _check_rows(what, g, padded=padded)
+    _check_rows(what, g, plan._layout)
     _check_plan_rows(what, g, plan, plan.num_tokens)
     if weights is None:
         raise Mp4jException(f"{what}: weights are needed (without them the backward is dispatchTokens along the plan)")
     weights = _check_weights(weights, plan, g)
-    nrows = plan.num_experts * plan.source_capacity if padded else sum(plan.send_counts)
     if not isinstance(slot_rows, torch.Tensor) or slot_rows.dim() < 1 or not slot_rows.is_contiguous():
         raise Mp4jException(f"{what}: slotRows must be the contiguous rows combineTokens(returnSlotRows=True) returned")
-    _check_plan_rows(f"{what}: slotRows", slot_rows, plan, nrows)
-    T, K = plan.num_tokens, plan.top_k
-    if _native_ok(g) and K <= COMBINE_BWD_MAX_TOP_K:
-        from ..ops.device_ops import moe_combine_backward
-        if padded:
-            send, _, _ = _pad_buffers(g, plan.num_experts, plan.source_capacity, len(plan.matrix), counts=False)
-            _, g_w = moe_combine_backward(g, slot_rows, plan.slots, weights, T, K, pad=(plan._route, plan.source_capacity),
-                                          out=(send, torch.empty((T, K), dtype=torch.float32, device=g.device)))
-        else:
-            send, g_w = moe_combine_backward(g, slot_rows, plan.slots, weights, T, K, max_slot=nrows - 1)
+    _check_plan_rows(f"{what}: slotRows", slot_rows, plan, sum(plan.send_counts))
+    if _native_ok(g) and plan.top_k <= COMBINE_BWD_MAX_TOP_K:
+        send, g_w = plan._layout.combine_backward(g, slot_rows, plan, weights)
     else:
         send, g_w = _torch_combine_backward(g, plan, weights, slot_rows)
-    g_w = g_w.view_as(weights)
-    if padded:
-        got, _ = _pad_exchange(engine, send, None, None, operand)
-        return _pad_regroup(got, plan, inverse=False), g_w
-    return _forward_rows(engine, send, plan, operand), g_w
+    return _to_experts(engine, send, plan, operand), g_w.view_as(weights)
 
 
 # ---------------------------------------------------------------- the grouped expert GEMM: its definition
@@ -681,57 +637,18 @@ def _check_source_capacity(source_capacity, capacity, capacity_factor):
         raise Mp4jException(f"dispatchTokens: sourceCapacity {S!r} is not an int >= 1")
 
 
-def _torch_pad(ids: torch.Tensor, nb: int, S: int):
-    """The torch form of the padded route: (slots int64[n], kept int64[nb], dropped int64[3])."""
-    counts, slots, order = _torch_route(ids, nb)
-    start = torch.cumsum(counts[:nb], 0) - counts[:nb]
-    e = ids.to(torch.int64)[order]
-    pe = torch.arange(order.numel(), dtype=torch.int64, device=ids.device) - start[e]
-    stay = pe < S
-    slots = torch.full_like(slots, -1)
-    slots[order[stay]] = e[stay] * S + pe[stay]
-    kept = counts[:nb].clamp(max=S)
-    dropped = torch.stack([(counts[:nb] - kept).sum(), counts[nb], counts[nb + 1]])
-    return slots, kept, dropped
-
-
-def _torch_pad_scatter(x: torch.Tensor, slots: torch.Tensor, top_k: int, row_scale: Optional[torch.Tensor],
-                       out: torch.Tensor):
-    """``out[slots[a]] = x[a // K]`` (times ``row_scale[a]``), every other row zero."""
-    out.zero_()
-    a = torch.nonzero(slots >= 0).reshape(-1)
-    rows = x[a // top_k]
-    if row_scale is not None:
-        s = row_scale.reshape(-1)[a].view((-1,) + (1,) * (x.dim() - 1))
-        rows = (s * rows.to(torch.float32)).to(x.dtype)
-    out[slots[a]] = rows
-    return out
-
-
-def _pad_buffers(x: torch.Tensor, E: int, S: int, p: int, counts: bool = True):
-    """(send rows ``[E*S, ...]``, the counts' wire int64 ``[p, el_pad]`` or None, el_pad).  On a GPU
-    both are views of ONE allocation, rows first: the copy plan stages them from one base address.
-    Every destination's counts start on a 16-byte boundary (el_pad = el rounded up to even)."""
+def _pad_buffers(x: torch.Tensor, E: int, S: int, p: int):
+    """(send rows ``[E*S, ...]``, the counts' wire int64 ``[p, el_pad]``, el_pad) of a padded dispatch.
+    On a GPU both are views of ONE allocation, rows first: the copy plan stages them from one base
+    address.  Every destination's counts start on a 16-byte boundary (el_pad = el rounded up to even)."""
     el = E // p
     el_pad = el + (el & 1)
     shape = (E * S,) + tuple(x.shape[1:])
     if not x.is_cuda:
-        wire = torch.empty((p, el_pad), dtype=torch.int64) if counts else None
-        return torch.empty(shape, dtype=x.dtype), wire, el_pad
+        return torch.empty(shape, dtype=x.dtype), torch.empty((p, el_pad), dtype=torch.int64), el_pad
     nbytes = E * S * _width(x.shape[1:]) * x.element_size()             # a multiple of 16 (_check_rows)
-    whole = torch.empty(nbytes + (p * el_pad * 8 if counts else 0), dtype=torch.uint8, device=x.device)
-    send = whole[:nbytes].view(x.dtype).view(shape)
-    wire = whole[nbytes:].view(torch.int64).view(p, el_pad) if counts else None
-    return send, wire, el_pad
-
-
-def _pad_scatter(x, route, top_k: int, E: int, S: int, row_scale, send):
-    """The padded route scatter into ``send``; returns the slots."""
-    if _native_ok(x):
-        from ..ops.device_ops import moe_route_scatter_pad
-        return moe_route_scatter_pad(route, x, top_k, send, S, row_scale=row_scale)
-    _torch_pad_scatter(x, route, top_k, row_scale, send)
-    return route
+    whole = torch.empty(nbytes + p * el_pad * 8, dtype=torch.uint8, device=x.device)
+    return whole[:nbytes].view(x.dtype).view(shape), whole[nbytes:].view(torch.int64).view(p, el_pad), el_pad
 
 
 def _pad_ipc_inst(engine, like: torch.Tensor, need_bytes: int):
@@ -809,56 +726,144 @@ def _pad_regroup(rows: torch.Tensor, plan: TokenPlan, inverse: bool) -> torch.Te
     local expert or one rank the two orders coincide and the result is a view."""
     p = len(plan.matrix)
     el, S = plan.num_experts // p, plan.source_capacity
-    if inverse:
-        if el == 1 or p == 1:
-            return rows.view((p * el * S,) + plan.row_shape)
-        return rows.view((el, p, S) + plan.row_shape).transpose(0, 1).contiguous().view((p * el * S,) + plan.row_shape)
-    if el == 1 or p == 1:
-        return rows.view((el, p * S) + plan.row_shape)
-    return rows.view((p, el, S) + plan.row_shape).transpose(0, 1).contiguous().view((el, p * S) + plan.row_shape)
+    if el > 1 and p > 1:
+        rows = rows.view(((el, p, S) if inverse else (p, el, S)) + plan.row_shape).transpose(0, 1).contiguous()
+    return rows.view(((p * el * S,) if inverse else (el, p * S)) + plan.row_shape)
 
 
-def _dispatch_padded(engine, x: torch.Tensor, ids: torch.Tensor, T: int, K: int, E: int, S: int, operand):
-    p, r = engine.p, engine.rank
-    el = E // p
-    engine._count("moe.dispatch.padded")
-    send, wire, el_pad = _pad_buffers(x, E, S, p)
-    if _native_ok(x):
-        from ..ops.device_ops import moe_pad_counts, moe_route_count
-        route = moe_route_count(ids, E)
-        _, dropped = moe_pad_counts(route, S, group=el, group_pad=el_pad, kept=wire.view(-1))
-        slots = _pad_scatter(x, route, K, E, S, None, send)
-    else:
-        slots, kept, dropped = _torch_pad(ids, E, S)
-        wire.zero_()
-        wire[:, :el] = kept.view(p, el)
-        route = slots
-        _torch_pad_scatter(x, slots, K, None, send)
-    const = (el * S,) * p
-    got, got_wire = _pad_exchange(engine, send, wire, el_pad, operand)
-    plan = TokenPlan(num_tokens=T, top_k=K, num_experts=E, expert_counts=(p * S,) * el, send_counts=const,
-                     recv_counts=const, slots=slots, matrix=(const,) * p, expert_matrix=None, demand_matrix=None,
-                     clipped=None, row_shape=tuple(x.shape[1:]), dtype=x.dtype, rank=r, source_capacity=S,
-                     kept=wire[:, :el].reshape(E), valid=got_wire[:, :el].t().contiguous(), dropped=dropped,
-                     _route=route)
-    return _pad_regroup(got, plan, inverse=False), plan
+# ---------------------------------------------------------------- the two layouts
+class _Ragged:
+    """Packed send order: ``sum(send_counts)`` rows, each written by the scatter.  One count exchange
+    makes the plan; the rows cross ranks by the ragged all-to-all with that matrix.  It holds no state: a
+    capacity's clip table is the plan's."""
+    has_pad_rows = capturable = False
+    regroup = staticmethod(_regroup)
+
+    def route(self, engine, x, ids, route, K, E, operand, capacity, capacity_factor):
+        p, r = engine.p, engine.rank
+        native = _native_ok(x)
+        counts = route.counts if native else route[0]
+        # the one count exchange: E + 2 numbers per rank
+        if p > 1:
+            from . import sparse
+            rows_ = sparse._count_matrix(engine, counts)
+        else:
+            rows_ = [counts.tolist()]
+        emat = tuple(tuple(int(v) for v in row[:E]) for row in rows_)
+        bad = [(j, int(row[E + 1])) for j, row in enumerate(rows_) if row[E + 1]]
+        if bad:
+            raise Mp4jException(f"dispatchTokens: rank {bad[0][0]} has {bad[0][1]} expert id(s) >= numExperts {E}")
+        # an expert capacity: every rank works out every rank's quota from the demand matrix
+        demand, clip, clipped = emat, None, 0
+        C = _resolve_capacity(capacity, capacity_factor, sum(int(v) for row in rows_ for v in row[:E + 1]), E)
+        if C is not None:
+            emat = capacity_quota(demand, C)
+            keep = emat[r]
+            clipped = sum(demand[r]) - sum(keep)
+            if native:                      # keep | its exclusive prefix: one small H2D copy
+                kbase = [0] + list(accumulate(keep))[:-1]
+                clip = torch.tensor(list(keep) + kbase, dtype=torch.int64).to(x.device)
+        if not native:                      # the torch form's route is its slots, clipped here
+            route = route[1] if C is None else _torch_clip(route, ids, E, emat[r])
+        el = E // p
+        mat = tuple(tuple(sum(emat[i][j * el:(j + 1) * el]) for j in range(p)) for i in range(p))
+        send_counts = mat[r]
+        send = torch.empty((sum(send_counts),) + tuple(x.shape[1:]), dtype=x.dtype, device=x.device)
+        slots = _scatter(self, x, route, K, None, send, clip)
+        got = self._a2a(engine, send, send_counts, mat, operand)
+        return got, dict(expert_counts=tuple(sum(emat[i][r * el + e] for i in range(p)) for e in range(el)),
+                         send_counts=send_counts, recv_counts=tuple(mat[i][r] for i in range(p)), slots=slots,
+                         matrix=mat, expert_matrix=emat, capacity=C, demand_matrix=demand, clipped=clipped,
+                         _route=route, _clip=clip)
+
+    def scatter(self, route, x, top_k, send, row_scale, clip):
+        from ..ops.device_ops import moe_route_scatter
+        return moe_route_scatter(route, x, top_k, send, row_scale=row_scale, placed=send.shape[0], clip=clip)
+
+    @staticmethod
+    def _a2a(engine, rows, counts, mat, operand):
+        if len(counts) == 1:
+            return rows                     # one rank: send order is expert-major already
+        return _exchange(engine, rows, counts, [list(row) for row in mat], operand)
+
+    def exchange(self, engine, rows, plan, operand, back):
+        if back:                            # the transposed matrix lands rows in the sender's slot order
+            return self._a2a(engine, rows, plan.recv_counts, zip(*plan.matrix), operand)
+        return self._a2a(engine, rows, plan.send_counts, plan.matrix, operand)
+
+    def check_expert_rows(self, rows, plan):
+        _check_rows("combineTokens", rows, self)
+        if rows.dim() >= 2 and tuple(rows.shape[2:]) == plan.row_shape and tuple(rows.shape[1:]) != plan.row_shape:
+            raise Mp4jException(f"combineTokens: rows {tuple(rows.shape)} are in the padded [experts, rows, ...] "
+                                f"layout, the plan is a ragged one (no sourceCapacity)")
+        _check_plan_rows("combineTokens", rows, plan, plan.num_rows)
+
+    def combine(self, back, plan, weights):
+        from ..ops.device_ops import moe_combine
+        return moe_combine(back, plan.slots, weights, plan.num_tokens, plan.top_k, max_slot=sum(plan.send_counts) - 1)
+
+    def combine_backward(self, g, slot_rows, plan, weights):
+        from ..ops.device_ops import moe_combine_backward
+        return moe_combine_backward(g, slot_rows, plan.slots, weights, plan.num_tokens, plan.top_k,
+                                    max_slot=sum(plan.send_counts) - 1)
 
 
-def _combine_padded(engine, expert_rows: torch.Tensor, plan: TokenPlan, weights, operand, return_slot_rows):
-    p = len(plan.matrix)
-    el, S = plan.num_experts // p, plan.source_capacity
-    want = (el, p * S) + plan.row_shape
-    if not isinstance(expert_rows, torch.Tensor) or tuple(expert_rows.shape) != want:
-        raise Mp4jException(f"combineTokens: the plan is a padded one (sourceCapacity {S}): rows must be "
-                            f"{want}, not {tuple(getattr(expert_rows, 'shape', ()))}")
-    if not expert_rows.is_contiguous() or expert_rows.dtype != plan.dtype or expert_rows.device != plan.slots.device:
-        raise Mp4jException(f"combineTokens: rows must be contiguous {plan.dtype} on {plan.slots.device}")
-    weights = _check_weights(weights, plan, expert_rows)
-    back, _ = _pad_exchange(engine, _pad_regroup(expert_rows, plan, inverse=True), None, None, operand)
-    T, K = plan.num_tokens, plan.top_k
-    if _native_ok(back):
+class _Padded:
+    """``E*S`` send rows, expert e's block at ``e*S``, the rows behind its kept ones zeros.  Every shape
+    is known before the ids are: no count exchange, nothing read back, nothing copied to the device."""
+    has_pad_rows = capturable = True
+    regroup = staticmethod(_pad_regroup)
+
+    def __init__(self, S: int):
+        self.S = S
+
+    def route(self, engine, x, ids, route, K, E, operand, *_no_capacity):
+        p, S = engine.p, self.S
+        el = E // p
+        engine._count("moe.dispatch.padded")
+        send, wire, el_pad = _pad_buffers(x, E, S, p)
+        if _native_ok(x):
+            from ..ops.device_ops import moe_pad_counts
+            _, dropped = moe_pad_counts(route, S, group=el, group_pad=el_pad, kept=wire.view(-1))
+        else:
+            route, kept, dropped = _torch_pad(route, ids, E, S)
+            wire.zero_()
+            wire[:, :el] = kept.view(p, el)
+        slots = _scatter(self, x, route, K, None, send)
+        got, got_wire = _pad_exchange(engine, send, wire, el_pad, operand)
+        const = (el * S,) * p
+        return got, dict(expert_counts=(p * S,) * el, send_counts=const, recv_counts=const, slots=slots,
+                         matrix=(const,) * p, expert_matrix=None, demand_matrix=None, clipped=None,
+                         kept=wire[:, :el].reshape(E), valid=got_wire[:, :el].t().contiguous(), dropped=dropped,
+                         _route=route)
+
+    def scatter(self, route, x, top_k, send, row_scale, _no_clip=None):
+        from ..ops.device_ops import moe_route_scatter_pad
+        return moe_route_scatter_pad(route, x, top_k, send, self.S, row_scale=row_scale)
+
+    def exchange(self, engine, rows, plan, operand, back):
+        return _pad_exchange(engine, rows, None, None, operand)[0]        # the same fixed exchange both ways
+
+    def check_expert_rows(self, rows, plan):
+        p = len(plan.matrix)
+        want = (plan.num_experts // p, p * self.S) + plan.row_shape
+        if not isinstance(rows, torch.Tensor) or tuple(rows.shape) != want:
+            raise Mp4jException(f"combineTokens: the plan is a padded one (sourceCapacity {self.S}): rows must be "
+                                f"{want}, not {tuple(getattr(rows, 'shape', ()))}")
+        if not rows.is_contiguous() or rows.dtype != plan.dtype or rows.device != plan.slots.device:
+            raise Mp4jException(f"combineTokens: rows must be contiguous {plan.dtype} on {plan.slots.device}")
+
+    def combine(self, back, plan, weights):
         from ..ops.device_ops import moe_combine_rows
-        out = moe_combine_rows(back, plan.slots, weights, T, K)
-    else:
-        out = _torch_combine(back, plan.slots, weights, T, K)
-    return (out, back) if return_slot_rows else out
+        return moe_combine_rows(back, plan.slots, weights, plan.num_tokens, plan.top_k)
+
+    def combine_backward(self, g, slot_rows, plan, weights):
+        from ..ops.device_ops import moe_combine_backward
+        return moe_combine_backward(g, slot_rows, plan.slots, weights, plan.num_tokens, plan.top_k,
+                                    pad=(plan._route, self.S))
+
+
+def _layout(source_capacity):
+    """The layout of a plan, chosen here and nowhere else: padded iff there is a per-source share."""
+    return _Ragged() if source_capacity is None else _Padded(source_capacity)
+

@@ -112,6 +112,36 @@ def test_a_share_above_all_demand_equals_the_uncapped_call():
     assert res == {0: [True] * 4, 1: [True] * 4}
 
 
+def _one_backward(comm, dtype):
+    """combineTokensBackward along a padded plan nothing is cut from and along the ragged plan of the
+    same ids: (g_weights equal, gradient rows equal block by block, the padded pad rows +0), as bits."""
+    r, p = comm.getRank(), comm.getSlaveNum()
+    T, K, E, S = 5, 2, 4, 10                 # S = T * K: no (rank, expert) demand reaches it
+    el = E // p
+    x = moe_ref.tokens(T, 8, dtype, 41 + r)
+    g = moe_ref.tokens(T, 8, dtype, 51 + r)
+    ids = ((torch.arange(T * K) * 3 + r) % E).view(T, K)
+    ids[2, 1] = -1
+    w = moe_ref.gate_weights(T, K, 7 + r)
+    rows_r, plan_r = comm.dispatchTokens(x, ids, E)
+    rows_p, plan_p = comm.dispatchTokens(x, ids, E, sourceCapacity=S)
+    _, back_r = comm.combineTokens(moe_ref.apply_experts(rows_r, plan_r.expert_counts, r * el), plan_r, w,
+                                   returnSlotRows=True)
+    _, back_p = comm.combineTokens(pad.apply_experts(rows_p, r * el), plan_p, w, returnSlotRows=True)
+    g_rows_r, g_w_r = comm.combineTokensBackward(g, plan_r, w, back_r)
+    g_rows_p, g_w_p = comm.combineTokensBackward(g, plan_p, w, back_p)
+    pieces = [g_rows_p[e, i * S:i * S + int(plan_p.valid[e, i])] for e in range(el) for i in range(p)]
+    return (same_bits(g_w_p, g_w_r), same_bits(torch.cat(pieces), g_rows_r) and g_rows_r.shape[0] > 0,
+            pad.pads_are_zero_bits(g_rows_p, plan_p.valid, S) and tuple(g_rows_p.shape) == (el, p * S, 8))
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
+@pytest.mark.parametrize("p", [1, 2])
+def test_the_two_layouts_give_one_combine_backward(p, dtype):
+    res, _, _ = run_ranks(p, _one_backward, args=(dtype,), timeout=120)
+    assert res == {r: (True, True, True) for r in range(p)}
+
+
 def _one_rank_and_bad_ids(comm):
     """p = 1 (no exchange at all) and ids >= E: slot -1, counted, never raised."""
     r, p = comm.getRank(), comm.getSlaveNum()
