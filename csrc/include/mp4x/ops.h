@@ -309,6 +309,27 @@ int mp4x_moe_combine_backward_pad(int dtype, const void* g, const void* rows, co
                                   int64_t T, int K, int64_t width, int64_t n, int nb, int64_t cap, void* scratch,
                                   size_t scratch_bytes, void* g_rows, float* g_weights, void* stream);
 
+// ---------------------------------------------------------------- K15 per-expert top-S select (drop by gate weight)
+// After mp4x_moe_route_count on the same ids (route_scratch is its scratch, read only): out_ids[a] =
+// ids[a] for the limit[e] assignments of every expert e = ids[a] in [0, nb) with the largest key
+// (gate_key(priority[a]), -a), compared lexicographically: the order-preserving map of the f32 bits
+// (unsigned order == float order, -0 folded onto +0, a positive NaN above +inf, a negative one below
+// -inf), ties to the lower a; -1 for the other assignments of e.  A negative id and an id >= nb pass
+// through.  limit[e] = limit_vec[e] (int64[nb], device memory, 8-byte aligned; a negative entry counts
+// as 0) or, with limit_vec NULL, the scalar limit >= 0.  out_ids has the ids' width and alignment and
+// is not ids.  masked[0] = the assignments turned into -1.  Expert e keeps exactly min(cnt[e],
+// limit[e]); with a constant priority they are its first ones.  An expert within its limit costs no
+// selection work; the others an 8-pass radix select over their contiguous words: work bounded by a
+// constant * n however the ids are distributed.  Integer arithmetic only, no global atomics, no host
+// read: deterministic and recordable in a graph.  scratch: 256-byte aligned,
+// mp4x_moe_priority_scratch_bytes(n, nb) bytes (0 for arguments the call refuses).  nb, n, pointers
+// and alignment as in mp4x_moe_route_count, else MP4X_E_BADARG before any launch; n == 0 writes
+// masked = 0 and needs nothing else.
+size_t mp4x_moe_priority_scratch_bytes(int64_t n, int nb);
+int mp4x_moe_priority_mask(const void* ids, int ids_are_i64, const float* priority, int64_t n, int nb, int64_t limit,
+                           const int64_t* limit_vec, const void* route_scratch, size_t route_scratch_bytes,
+                           void* out_ids, int64_t* masked, void* scratch, size_t scratch_bytes, void* stream);
+
 // ---------------------------------------------------------------- errors
 // Reads and clears this thread's last HIP error.  mp4x reports its own failures through return
 // codes; a failed HIP call must not stay "last error" for PyTorch's next kernel-launch check to

@@ -41,16 +41,18 @@ from ..parallel.moe import combine_weight_grad_torch
 
 class _Dispatch(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, comm, expert_ids, num_experts, operand, capacity, capacity_factor, source_capacity):
+    def forward(ctx, x, comm, expert_ids, num_experts, operand, capacity, capacity_factor, source_capacity,
+                priority=None):
+        extra = {} if priority is None else {"priority": priority}      # (None: the call as it always was)
         rows, plan = comm.dispatchTokens(x.contiguous(), expert_ids, num_experts, operand=operand, capacity=capacity,
-                                         capacityFactor=capacity_factor, sourceCapacity=source_capacity)
+                                         capacityFactor=capacity_factor, sourceCapacity=source_capacity, **extra)
         ctx.comm, ctx.plan, ctx.operand = comm, plan, operand
         return rows, plan
 
     @staticmethod
     def backward(ctx, g_rows, _plan=None):
         gx = ctx.comm.combineTokens(g_rows.contiguous(), ctx.plan, None, operand=ctx.operand)
-        return gx, None, None, None, None, None, None, None
+        return gx, None, None, None, None, None, None, None, None
 
 
 class _Combine(torch.autograd.Function):
@@ -78,12 +80,17 @@ class _Combine(torch.autograd.Function):
 
 
 def dispatch_tokens(comm, x: torch.Tensor, expert_ids: torch.Tensor, num_experts: int, operand=None, capacity=None,
-                    capacity_factor=None, source_capacity=None):
+                    capacity_factor=None, source_capacity=None, priority=None):
     """Differentiable ``comm.dispatchTokens``: ``(rows, plan)``.  With an expert capacity, or a
     per-source share (``source_capacity``: the padded layout, ``rows`` ``[E/p, p*S, ...]``), a
     clipped assignment has slot -1 in the plan: it takes no part in either backward pass (no
-    gradient reaches its token through it, and its gate weight's gradient is 0)."""
-    return _Dispatch.apply(x, comm, expert_ids, num_experts, operand, capacity, capacity_factor, source_capacity)
+    gradient reaches its token through it, and its gate weight's gradient is 0).  ``priority``
+    (float32 ``[T, K]``, see ``dispatchTokens``) only chooses which assignments those are: it is not
+    differentiated."""
+    if priority is None:
+        return _Dispatch.apply(x, comm, expert_ids, num_experts, operand, capacity, capacity_factor, source_capacity)
+    return _Dispatch.apply(x, comm, expert_ids, num_experts, operand, capacity, capacity_factor, source_capacity,
+                           priority.detach())
 
 
 COMBINE_BACKWARDS = ("torch", "fused")
@@ -342,6 +349,9 @@ def route_topk_grouped(logits: torch.Tensor, top_k: int, *, score: str = "sigmoi
                                                ids_dtype, bool(stats), True))
 
 
+DROP_POLICIES = ("position", "probs")
+
+
 class ExpertParallelMoE(torch.nn.Module):
     """Top-k routed mixture of two-layer ReLU MLP experts, experts sharded over the ranks.
 
@@ -385,15 +395,26 @@ class ExpertParallelMoE(torch.nn.Module):
     ``combine_backward="fused"`` takes the combine's two gradients from one pass over the output
     gradient (:func:`combine_tokens` with ``backward="fused"``, the K11 kernel on the GPU) instead of
     a second dispatch and a ``[T, K, d_model]`` product in torch.  The default ``"torch"`` is the
-    layer as it was."""
+    layer as it was.
+
+    ``drop_policy`` says which assignments a ``capacity_factor`` or a ``source_capacity`` drops:
+    ``"position"`` (the default, the layer as it was) the last ones in (token, k) order, ``"probs"`` the
+    ones with the lowest gate weight (``dispatchTokens(priority=)`` with the detached gate weights: the
+    K15 select on the GPU; ties go to the earlier assignment).  ``"probs"`` without either capacity is
+    refused.  A dropped assignment's gate weight gets gradient +0 either way."""
 
     def __init__(self, comm, d_model: int, d_hidden: int, num_experts: int, top_k: int, seed: int = 0,
                  device=None, dtype=torch.float32, operand=None, capacity_factor=None, source_capacity=None,
                  router: str = "torch", renormalize: bool = False, aux_loss_coef: float = 0.0,
                  z_loss_coef: float = 0.0, combine_backward: str = "torch", score: str = "softmax",
                  expert_groups: Optional[int] = None, topk_groups: Optional[int] = None, routed_scale: float = 1.0,
-                 balance_bias: bool = False):
+                 balance_bias: bool = False, drop_policy: str = "position"):
         super().__init__()
+        if drop_policy not in DROP_POLICIES:
+            raise ValueError(f"drop_policy {drop_policy!r} is not 'position' or 'probs'")
+        if drop_policy == "probs" and capacity_factor is None and source_capacity is None:
+            raise ValueError("drop_policy='probs' needs capacity_factor or source_capacity: nothing is dropped without one")
+        self.drop_policy = drop_policy
         if combine_backward not in COMBINE_BACKWARDS:
             raise ValueError(f"combine_backward {combine_backward!r} is not 'torch' or 'fused'")
         self.combine_backward = combine_backward
@@ -486,7 +507,8 @@ class ExpertParallelMoE(torch.nn.Module):
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         w, ids = self.route_fused(x) if self.router_kind == "fused" else self.route(x)
         rows, plan = dispatch_tokens(self.comm, x, ids, self.num_experts, self.operand,
-                                     capacity_factor=self.capacity_factor, source_capacity=self.source_capacity)
+                                     capacity_factor=self.capacity_factor, source_capacity=self.source_capacity,
+                                     priority=w.detach().contiguous() if self.drop_policy == "probs" else None)
         self.last_plan = plan
         if self.source_capacity is not None:
             # [el, p*S, d]: one pair of batched GEMMs whatever the ids were (a pad row's output is the

@@ -644,6 +644,45 @@ def moe_combine_rows(rows: torch.Tensor, slots: torch.Tensor, weights: Optional[
     return out
 
 
+def moe_priority_mask(rc: RouteCount, priority: torch.Tensor, limit, out: Optional[torch.Tensor] = None,
+                      stream=None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """K15, the per-expert top-S select after :func:`moe_route_count`: ``(ids_out, masked)``.
+    ``ids_out[a] = rc.ids[a]`` for the ``limit[e]`` assignments of every expert e with the largest
+    ``(gate key of priority[a], -a)`` (float order with -0 == +0, a positive NaN above +inf, a negative
+    one below -inf; ties to the lower a), -1 for the expert's other assignments; a negative id and an
+    id >= nb pass through.  ``priority``: float32, one per assignment.  ``limit``: an int >= 0 for every
+    expert, or an int64 ``[nb]`` tensor on the ids' device (a negative entry counts as 0).  ``masked``:
+    int64 ``[1]`` on the device, the assignments turned into -1.  ``out``: write there (the ids' dtype
+    and size, not the ids themselves).  Nothing is read back and the result is identical run to run."""
+    ids = rc.ids
+    _dev_check(ids, priority, out, limit if isinstance(limit, torch.Tensor) else None)
+    n = ids.numel()
+    if priority.dtype != torch.float32 or priority.numel() != n:
+        raise ValueError(f"moe_priority_mask: priority must be float32, one per assignment ({n})")
+    if isinstance(limit, torch.Tensor):
+        if limit.dtype != torch.int64 or tuple(limit.shape) != (rc.nb,):
+            raise ValueError(f"moe_priority_mask: a limit tensor must be int64 [{rc.nb}]")
+        scalar, vec = 0, limit.data_ptr()
+    else:
+        if isinstance(limit, bool) or not isinstance(limit, int) or not 0 <= limit < 2 ** 63:
+            raise ValueError(f"moe_priority_mask: the limit {limit!r} is not an int >= 0 or an int64 [{rc.nb}] tensor")
+        scalar, vec = limit, None
+    if out is None:
+        out = torch.empty_like(ids)
+    elif out.dtype != ids.dtype or out.numel() != n or out.data_ptr() == ids.data_ptr() and n:
+        raise ValueError("moe_priority_mask: out must have the ids' dtype and size and be another tensor")
+    lib = native.hip()
+    sb = lib.mp4x_moe_priority_scratch_bytes(n, rc.nb)
+    scratch = torch.empty(max(sb, 1), dtype=torch.uint8, device=ids.device)
+    masked = torch.empty(1, dtype=torch.int64, device=ids.device)
+    check(lib.mp4x_moe_priority_mask(ids.data_ptr() if n else None, int(ids.dtype == torch.int64),
+                                     priority.data_ptr() if n else None, n, rc.nb, scalar, vec,
+                                     rc.scratch.data_ptr() if n else None, rc.scratch.numel() if n else 0,
+                                     out.data_ptr() if n else None, masked.data_ptr(), scratch.data_ptr(), sb,
+                                     stream_ptr(stream)), "mp4x_moe_priority_mask")
+    return out, masked
+
+
 MOE_COMBINE_BWD_MAX_TOP_K = 16       # csrc/kernels/moe.hip: kMoeBwdMaxK
 
 

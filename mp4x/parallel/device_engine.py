@@ -1682,18 +1682,21 @@ class DeviceEngine(AutotuneMixin, ScheduleMixin, RootedMixin):
 
     # ================================================================== expert-parallel routing
     def dispatch_tokens(self, x: torch.Tensor, expert_ids: torch.Tensor, num_experts: int, operand=None,
-                        plan=None, row_scale=None, capacity=None, capacity_factor=None, source_capacity=None):
+                        plan=None, row_scale=None, capacity=None, capacity_factor=None, source_capacity=None,
+                        priority=None):
         """Token rows to the ranks that own their experts, grouped by local expert
         (parallel/moe.py).  ``capacity`` / ``capacity_factor``: every expert accepts its first C
         assignments in (source rank, assignment) order; the others are clipped in the route
         scatter.  ``source_capacity``: the padded fixed-capacity layout (every source rank sends at
-        most S rows to every expert; no count exchange, no host sync, capturable).  ``plan`` + ``row_scale``: dispatch again along an earlier plan (and its
+        most S rows to every expert; no count exchange, no host sync, capturable).  ``priority`` (with any of
+        these): drop by gate weight instead of by position (K15).  ``plan`` + ``row_scale``: dispatch again along an earlier plan (and its
         clipping), rows scaled per assignment (the combine's backward), with no count exchange."""
         from . import moe
         self._count("moe.dispatch")
         if plan is not None:
             return moe.dispatch_scaled(self, x, plan, row_scale, operand), plan
-        return moe.dispatch(self, x, expert_ids, num_experts, operand, capacity, capacity_factor, source_capacity)
+        return moe.dispatch(self, x, expert_ids, num_experts, operand, capacity, capacity_factor, source_capacity,
+                            priority=priority)
 
     def combine_tokens(self, expert_rows: torch.Tensor, plan, weights=None, operand=None, return_slot_rows=False):
         """Expert rows back to their tokens, every token's K rows summed with its weights in k

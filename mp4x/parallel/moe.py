@@ -48,6 +48,15 @@ count exchange, no host sync, and the pair can be recorded by ``DeviceEngine.cap
 A padded dispatch -> experts -> combine is, bit for bit, the uncapped call on the ids with every
 assignment past its per-(rank, expert) share replaced by -1 (``tests/moe_padded_ref.py``).
 
+Drop by gate weight (``priority=``, with any of the capacities above): where a rank must drop
+assignments of an expert it keeps the ones with the largest ``(gate key of priority[a], -a)`` instead of
+the first ones (:func:`priority_mask_torch` is the definition; K15, ``csrc/kernels/moe_priority.hip``, on
+the GPU).  The ids with the losers set to -1 are counted again and take the position path, which then
+has nothing left to drop: padded, the limit is the scalar S; ragged with a capacity, the limit is this
+rank's quota ``keep[r]`` of the unchanged count exchange, so quotas between ranks stay in rank order and
+the priority decides inside a rank.  The plan's route is the masked one and it has no clip table, so
+every later combine and backward follows it unchanged.
+
 The combine's backward (``combine_backward``, ``combineTokensBackward``) makes both of its gradients
 from the output gradient ``g``: the expert rows' is ``g`` dispatched again along the plan with the
 gate weights as row scale, the weights' the dot of ``g[t]`` with every slot row of token t.  Both
@@ -285,6 +294,71 @@ def _resolve_capacity(capacity, capacity_factor, assignments: int, E: int) -> Op
     return capacity
 
 
+# ---------------------------------------------------------------- drop by gate weight (K15)
+def priority_mask_torch(ids: torch.Tensor, priority: torch.Tensor, nb: int, limit):
+    """The definition of the per-expert top-S select in torch, and its CPU form: ``(out, masked)``.
+    ``out[a] = ids[a]`` for the ``limit[e]`` assignments of every expert ``e = ids[a]`` in ``[0, nb)``
+    with the largest ``(gate key of priority[a], -a)``, -1 for the expert's others; a negative id and
+    an id ``>= nb`` pass through.  ``masked``: int64 ``[1]``, the assignments turned into -1.  ``limit``:
+    an int or an int64 ``[nb]`` tensor (negative: 0).  The key comes from the float's bits by integer
+    operations (unsigned order == float order, -0 folded onto +0, a positive NaN above +inf, a
+    negative one below -inf) and the order from two stable sorts, by key descending and then by id: no
+    float is ever compared."""
+    flat = ids.reshape(-1)
+    i64 = flat.to(torch.int64)
+    n = i64.numel()
+    bits = priority.reshape(-1).contiguous().view(torch.int32).to(torch.int64) & 0xffffffff
+    bits = torch.where((bits & 0x7fffffff) == 0, torch.zeros_like(bits), bits)
+    key = torch.where((bits >> 31) != 0, bits ^ 0xffffffff, bits ^ 0x80000000)
+    placed = (i64 >= 0) & (i64 < nb)
+    bucket = torch.where(placed, i64, torch.full_like(i64, nb))
+    by_key = torch.argsort(0xffffffff - key, stable=True)               # equal keys: the lower a first
+    order = by_key[torch.argsort(bucket[by_key], stable=True)]
+    counts = torch.bincount(bucket, minlength=nb + 1)
+    start = torch.cumsum(counts, 0) - counts
+    if isinstance(limit, torch.Tensor):
+        lim = limit.to(device=i64.device, dtype=torch.int64).reshape(-1)
+    else:
+        lim = torch.full((nb,), int(limit), dtype=torch.int64, device=i64.device)
+    lim = torch.cat([lim, counts[nb:]])                                   # the bucket of the unplaced keeps all
+    b = bucket[order]
+    rank = torch.arange(n, dtype=torch.int64, device=i64.device) - start[b]
+    gone = order[rank >= lim[b]]
+    out = flat.clone()
+    out[gone] = -1
+    return out.view(ids.shape), torch.full((1,), gone.numel(), dtype=torch.int64, device=i64.device)
+
+
+def _check_priority(priority, expert_ids: torch.Tensor, x: torch.Tensor, any_capacity: bool):
+    """The caller's contract for ``priority``; returns it flattened, or None."""
+    if priority is None:
+        return None
+    if not any_capacity:
+        raise Mp4jException("dispatchTokens: priority needs capacity, capacityFactor or sourceCapacity: nothing is "
+                            "dropped without one")
+    T = expert_ids.shape[0]
+    K = 1 if expert_ids.dim() == 1 else int(expert_ids.shape[1])
+    ok = (isinstance(priority, torch.Tensor) and priority.dtype == torch.float32 and priority.device == x.device
+          and (tuple(priority.shape) == (T, K) or (K == 1 and tuple(priority.shape) == (T,)))
+          and priority.is_contiguous())
+    if not ok:
+        raise Mp4jException(f"dispatchTokens: priority must be a contiguous float32 [{T}, {K}] tensor on {x.device}")
+    return priority.reshape(-1)
+
+
+def _priority_route(x: torch.Tensor, ids: torch.Tensor, route, E: int, priority: torch.Tensor, limit):
+    """The route of a priority call: the top ``limit[e]`` of every expert keep their id, the route is
+    counted again on those ids, and everything behind it is the position path with nothing left to
+    drop.  Returns (those ids, their route, masked int64 [1], the counts of the caller's ids); all on
+    the device."""
+    if _native_ok(x):
+        from ..ops.device_ops import moe_priority_mask, moe_route_count
+        ids_m, masked = moe_priority_mask(route, priority, limit)
+        return ids_m, moe_route_count(ids_m, E), masked, route.counts
+    ids_m, masked = priority_mask_torch(ids, priority, E, limit)
+    return ids_m, _torch_route(ids_m, E), masked, route[0]
+
+
 # ---------------------------------------------------------------- count matrix, regroup
 def _segments(plan: TokenPlan) -> List[Tuple[int, int, int]]:
     """(expert-major row offset, source-major row offset, rows) of every (source, local expert)
@@ -353,7 +427,7 @@ def _scatter(layout, x: torch.Tensor, route, top_k: int, row_scale: Optional[tor
 
 
 def dispatch(engine, x: torch.Tensor, expert_ids: torch.Tensor, num_experts: int, operand=None, capacity=None,
-             capacity_factor=None, source_capacity=None):
+             capacity_factor=None, source_capacity=None, priority=None):
     """``(rows, plan)``: see ``ProcessCommSlave.dispatchTokens``."""
     p = engine.p
     E = int(num_experts)
@@ -375,6 +449,8 @@ def dispatch(engine, x: torch.Tensor, expert_ids: torch.Tensor, num_experts: int
     if K < 1:
         raise Mp4jException("dispatchTokens: expertIds needs at least one column")
     ids = expert_ids.reshape(-1).contiguous()
+    priority = _check_priority(priority, expert_ids, x, source_capacity is not None or capacity is not None
+                               or capacity_factor is not None)
     # the first half of the route: K9's histogram + scan, or its torch form
     if _native_ok(x):
         from ..ops.device_ops import moe_route_count
@@ -382,7 +458,10 @@ def dispatch(engine, x: torch.Tensor, expert_ids: torch.Tensor, num_experts: int
     else:
         route = _torch_route(ids, E)
     # the layout's: which counts cross ranks, the scatter, the exchange and what the plan says of them
-    got, fields = layout.route(engine, x, ids, route, K, E, operand, capacity, capacity_factor)
+    if priority is None:
+        got, fields = layout.route(engine, x, ids, route, K, E, operand, capacity, capacity_factor)
+    else:
+        got, fields = layout.route(engine, x, ids, route, K, E, operand, capacity, capacity_factor, priority=priority)
     plan = TokenPlan(num_tokens=T, top_k=K, num_experts=E, row_shape=tuple(x.shape[1:]), dtype=x.dtype,
                      rank=engine.rank, source_capacity=source_capacity, _layout=layout, **fields)
     return layout.regroup(got, plan, inverse=False), plan
@@ -739,7 +818,7 @@ class _Ragged:
     has_pad_rows = capturable = False
     regroup = staticmethod(_regroup)
 
-    def route(self, engine, x, ids, route, K, E, operand, capacity, capacity_factor):
+    def route(self, engine, x, ids, route, K, E, operand, capacity, capacity_factor, priority=None):
         p, r = engine.p, engine.rank
         native = _native_ok(x)
         counts = route.counts if native else route[0]
@@ -763,7 +842,16 @@ class _Ragged:
             if native:                      # keep | its exclusive prefix: one small H2D copy
                 kbase = [0] + list(accumulate(keep))[:-1]
                 clip = torch.tensor(list(keep) + kbase, dtype=torch.int64).to(x.device)
-        if not native:                      # the torch form's route is its slots, clipped here
+        if priority is not None:
+            # drop by gate weight: the quota keep[e] is the position call's (between ranks the capacity
+            # is still handed out in rank order); inside this rank the top keep[e] of expert e stay.
+            # The plan's route is the one of the masked ids and nothing is left to clip
+            limit = clip[:E] if native else torch.tensor(list(emat[r]), dtype=torch.int64)
+            route = _priority_route(x, ids, route, E, priority, limit)[1]
+            clip = None
+            if not native:
+                route = route[1]
+        elif not native:                    # the torch form's route is its slots, clipped here
             route = route[1] if C is None else _torch_clip(route, ids, E, emat[r])
         el = E // p
         mat = tuple(tuple(sum(emat[i][j * el:(j + 1) * el]) for j in range(p)) for i in range(p))
@@ -817,11 +905,14 @@ class _Padded:
     def __init__(self, S: int):
         self.S = S
 
-    def route(self, engine, x, ids, route, K, E, operand, *_no_capacity):
+    def route(self, engine, x, ids, route, K, E, operand, *_no_capacity, priority=None):
         p, S = engine.p, self.S
         el = E // p
         engine._count("moe.dispatch.padded")
         send, wire, el_pad = _pad_buffers(x, E, S, p)
+        masked = None
+        if priority is not None:            # drop by gate weight: the top S of every expert, then the position path
+            ids, route, masked, counts = _priority_route(x, ids, route, E, priority, S)
         if _native_ok(x):
             from ..ops.device_ops import moe_pad_counts
             _, dropped = moe_pad_counts(route, S, group=el, group_pad=el_pad, kept=wire.view(-1))
@@ -829,6 +920,10 @@ class _Padded:
             route, kept, dropped = _torch_pad(route, ids, E, S)
             wire.zero_()
             wire[:, :el] = kept.view(p, el)
+        if masked is not None:
+            # `dropped` keeps its meaning: past the share | negative | >= E, of the caller's ids (the
+            # masked route has nothing past its share and counts the masked ones as negative)
+            dropped = torch.cat([masked, counts[E:E + 2]])
         slots = _scatter(self, x, route, K, None, send)
         got, got_wire = _pad_exchange(engine, send, wire, el_pad, operand)
         const = (el * S,) * p

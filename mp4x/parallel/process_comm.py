@@ -947,7 +947,7 @@ class ProcessCommSlave:
         return self.device.all_to_all_v(sendData, list(sendCounts), recvData, operand)
 
     def dispatchTokens(self, x, expertIds, numExperts: int, operand: Optional[Operand] = None, capacity=None,
-                       capacityFactor=None, sourceCapacity=None):
+                       capacityFactor=None, sourceCapacity=None, priority=None):
         """Expert-parallel token dispatch (extension, over ``alltoallArray``'s transport).
 
         ``x`` is ``[T, ...]`` (contiguous; f32 / bf16 / f16), ``expertIds`` ``[T, K]`` or ``[T]``
@@ -1003,19 +1003,35 @@ class ProcessCommSlave:
         ``capacityFactor`` (both need the demand matrix); ``operand`` goes to the exact
         all-to-all with the constant count matrix outside a capture.
 
+        Drop by gate weight: ``priority`` (float32, ``expertIds``' shape, contiguous, on ``x``'s
+        device; needs one of the capacities above).  Where the call drops assignments of an expert
+        on this rank it then keeps the ones with the largest priority instead of the first ones:
+        the order is the float order with -0 equal to +0, a positive NaN above +inf and a negative
+        one below -inf, and equal priorities go to the lower ``t*K + k``, so a constant priority is
+        the position policy.  With ``sourceCapacity=S`` every expert keeps this rank's top S; with a
+        capacity rank i still keeps ``keep[i][e]`` rows of expert e: the quotas between ranks stay
+        in rank order, the priority decides inside a rank.  The call equals, bit for bit, the
+        position call on the ids with every assignment it drops set to -1 (rows, slots, ``kept``,
+        ``valid``, every later combine and backward), and every host-side field of the plan equals
+        the position call's; ``plan.dropped`` keeps its meaning.  On a GPU the selection is the K15
+        kernels (a radix select per overflowing expert): no host sync, capturable with the padded
+        layout.  It is not differentiated.
+
         Raises :class:`Mp4jException`, on every rank alike and before any row moves, for ``E``
         not a multiple of the rank count or above 2048, mismatched shapes, an id ``>= E`` on any
         rank (the message names the rank), another dtype, GPU rows that are not whole 16-byte
         vectors, both ``capacity`` and ``capacityFactor``, a ``capacity`` that is not an int
         ``>= 1`` (a bool is refused), a ``capacityFactor`` that is not a finite number ``> 0``,
-        a ``sourceCapacity`` that is not an int ``>= 1`` or that comes with a capacity, and,
+        a ``sourceCapacity`` that is not an int ``>= 1`` or that comes with a capacity, a
+        ``priority`` without any capacity or of another dtype, shape, layout or device, and,
         without ``sourceCapacity``, a call inside a graph capture (the count exchange is a host
         sync)."""
         self._tick("dispatchTokens")
         if not _is_torch(x):
             raise Mp4jException("dispatchTokens needs a torch tensor (device engine)")
         return self.device.dispatch_tokens(x, expertIds, numExperts, operand, capacity=capacity,
-                                           capacity_factor=capacityFactor, source_capacity=sourceCapacity)
+                                           capacity_factor=capacityFactor, source_capacity=sourceCapacity,
+                                           priority=priority)
 
     def combineTokens(self, expertRows, plan, weights=None, operand: Optional[Operand] = None,
                       returnSlotRows: bool = False):
