@@ -156,6 +156,18 @@ int mp4x_hash_rbk_supported(int dtype, int op);
 int mp4x_hash_reduce_by_key(int dtype, int op, const int64_t* keys, int64_t n, const void* vals, int64_t dim,
                             void* scratch, size_t scratch_bytes, int64_t* out_keys, void* out_vals,
                             int32_t* out_count, int64_t* m_flag, void* stream);
+// K5c: the hash reduce-by-key with an output that is a function of the input alone (the same
+// arguments and refusals as mp4x_hash_reduce_by_key; n == 0 gives m = 0).  out_keys[m]: the occupied
+// slots, in slot order, of the canonical table (table_slots(n) slots, splitmix64 homes, the distinct
+// keys other than -1 inserted in ascending unsigned order by plain linear probing:
+// csrc/kernels/sparse_hash_map.hpp), then the run of rows keyed -1, if any.  out_vals[u] combines the
+// run's rows in ascending input index whatever its length: the sort path's values bit for bit.
+// m_flag[0] = m; m_flag[1] != 0 when a lane passed a loop bound (then nothing else is meaningful:
+// use the sort path).  No allocation, no host read.
+size_t mp4x_hash_rbk_canonical_scratch_bytes(int64_t n);
+int mp4x_hash_reduce_by_key_canonical(int dtype, int op, const int64_t* keys, int64_t n, const void* vals, int64_t dim,
+                                      void* scratch, size_t scratch_bytes, int64_t* out_keys, void* out_vals,
+                                      int32_t* out_count, int64_t* m_flag, void* stream);
 // K5d: keys[n] with k / stride - base in [0, T) (e.g. an owner's share of dense ids, stride = p),
 // vals[n][dim] (or NULL: keys only) -> out_keys[m] ascending, out_vals[m][dim] (rows combined in
 // input order: the sort path's result bit for bit), out_count[m] (optional); m_flag[0] = m,

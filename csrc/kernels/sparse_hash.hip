@@ -27,6 +27,15 @@
 // integer data and MAX / MIN are exact either way); the FIRST rule (K8) is not served.  Rows
 // whose key equals -1 (the EMPTY marker) form a side run of their own.
 //
+// K5c (mp4x_hash_reduce_by_key_canonical) is the hash path with those differences removed, for a
+// caller that needs the output to be a function of the input: the table is the CANONICAL one
+// (sparse_hash_map.hpp: plain linear probing of the distinct keys in ascending unsigned order,
+// reached from any insertion order by priority insertion, k_hashc_insert), the rows are linked
+// by a second, read-only probe when the table is final (k_hashc_link), the runs are numbered in
+// slot order by K5d's count / scan / compact (no atomic on the run counter; the -1 run last),
+// and every run, however long, combines in ascending row index.  Every loop is bounded; a lane
+// past a bound sets m_flag[1] and the caller takes the sort path.
+//
 // K5d (below) is the identity-hash form for DENSE keys (k / stride - base in [0, T)): no
 // probing, an ordered compaction, so the keys come out ascending — the sort path's result and
 // order — and the tensor forms take it by default where the carried key range allows.
@@ -34,22 +43,16 @@
 #include <type_traits>
 
 #include "common.hpp"
+#include "sparse_hash_map.hpp"
 
 namespace mp4x {
 
 namespace {
-constexpr unsigned long long kHashEmpty = ~0ull;
+using hmap::hash_mix;
+using hmap::table_slots;
+constexpr unsigned long long kHashEmpty = hmap::kEmpty;
 constexpr int kCompactPer = 4;             // slots per lane in k_hash_compact (>= 2 blocks per CU at 2n = 400k)
 constexpr int kOrderMax = 64;              // longest run whose rows are put in input order
-
-__device__ __forceinline__ uint64_t hash_mix(uint64_t k) {   // splitmix64 finalizer
-  k ^= k >> 30;
-  k *= 0xbf58476d1ce4e5b9ull;
-  k ^= k >> 27;
-  k *= 0x94d049bb133111ebull;
-  k ^= k >> 31;
-  return k;
-}
 
 // The side run of rows keyed -1 (the EMPTY marker): its list head and, once compacted, its run.
 struct SideRun {
@@ -92,6 +95,80 @@ __global__ __launch_bounds__(kBlock) void k_hash_insert(const int64_t* __restric
         }
         if (cur == k) break;
         h = (h + 1) & mask;
+      }
+      head = &thead[h];
+    }
+    next[i] = atomicExch(head, (int32_t)i);              // push row i on its run's list
+  }
+}
+
+// ---------------------------------------------------------------- K5c: the canonical table
+// The table as a function of the key SET (sparse_hash_map.hpp): priority linear probing, the
+// smaller unsigned key wins a slot and the displaced key moves on.  No row lists here: a row's
+// slot is final only when every row is in.  A lane past one of the header's two bounds sets
+// m_flag[1] and stops (the caller then takes the sort path): nothing spins without a bound.
+__global__ __launch_bounds__(kBlock) void k_hashc_insert(const int64_t* __restrict__ keys, int64_t n,
+                                                         unsigned long long* __restrict__ tkeys, uint64_t mask,
+                                                         uint64_t max_advance, uint64_t max_iter,
+                                                         unsigned long long* __restrict__ m_flag) {
+  const int64_t nthr = (int64_t)gridDim.x * kBlock;
+  for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += nthr) {
+    unsigned long long v = (unsigned long long)keys[i];
+    if (v == kHashEmpty) continue;                       // the side run: k_hashc_link
+    uint64_t h = hmap::home(v, mask);
+    uint64_t adv = 0, it = 0;
+    unsigned long long c = __hip_atomic_load(&tkeys[h], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    for (;;) {
+      if (++it > max_iter) {
+        atomicOr(&m_flag[1], 1ull);
+        break;
+      }
+      const int act = hmap::step(c, v);
+      if (act == hmap::kDone) break;
+      if (act == hmap::kSwap) {
+        const unsigned long long old = atomicCAS(&tkeys[h], c, v);
+        if (old != c) {                                  // lost: step again on the slot's new value
+          c = old;
+          continue;
+        }
+        if (c == kHashEmpty) break;                      // took an empty slot: nothing to carry on
+        v = c;                                           // the displaced key moves on
+      }
+      if (++adv >= max_advance) {
+        atomicOr(&m_flag[1], 1ull);
+        break;
+      }
+      h = (h + 1) & mask;
+      c = __hip_atomic_load(&tkeys[h], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+  }
+}
+
+// A launch of its own, when the table is final: every row finds its key's slot by a read-only
+// probe from the key's home (at most max_advance slots; an empty slot or the bound means the
+// insert gave up: m_flag[1]) and is pushed on the slot's list.  Rows keyed -1: the side run.
+__global__ __launch_bounds__(kBlock) void k_hashc_link(const int64_t* __restrict__ keys, int64_t n,
+                                                       const unsigned long long* __restrict__ tkeys,
+                                                       int32_t* __restrict__ thead, uint64_t mask,
+                                                       uint64_t max_advance, int32_t* __restrict__ next,
+                                                       SideRun* __restrict__ side,
+                                                       unsigned long long* __restrict__ m_flag) {
+  const int64_t nthr = (int64_t)gridDim.x * kBlock;
+  for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += nthr) {
+    const unsigned long long k = (unsigned long long)keys[i];
+    int32_t* head = &side->head;
+    if (k != kHashEmpty) {
+      uint64_t h = hmap::home(k, mask);
+      uint64_t adv = 0;
+      unsigned long long cur = tkeys[h];
+      while (cur != k && cur != kHashEmpty && ++adv < max_advance) {
+        h = (h + 1) & mask;
+        cur = tkeys[h];
+      }
+      if (cur != k) {                                    // not in the table
+        atomicOr(&m_flag[1], 1ull);
+        next[i] = -1;
+        continue;
       }
       head = &thead[h];
     }
@@ -158,8 +235,11 @@ constexpr int kMinG = 4;                   // lanes per run at least (bounds the
 // G lanes per run, 64 / G runs per wave.  Unit = a 16-byte vector of W elements (VEC) or one
 // element; `units` per row.  Lane 0 of a group walks the run's list into its LDS list (ascending
 // insertion: runs up to kOrderMax rows), the group combines the rows in that order, two in flight.
-// A longer run combines in list order (walking the list again).
-template <int DT, int OP, bool VEC>
+// A longer run combines in list order (walking the list again) — or, with ORDERED (K5c), in
+// ascending row index as well, in batches of kOrderMax rows: for every batch the walker walks the
+// list once more and keeps the kOrderMax smallest indices above the previous batch's largest (the
+// same sorted insertion), O(L^2 / kOrderMax) list steps for a run of L rows.
+template <int DT, int OP, bool VEC, bool ORDERED = false>
 __global__ __launch_bounds__(kBlock) void k_hash_reduce(const int32_t* __restrict__ rhead,
                                                         const int32_t* __restrict__ next,
                                                         const unsigned long long* __restrict__ m_dev,
@@ -216,6 +296,31 @@ __global__ __launch_bounds__(kBlock) void k_hash_reduce(const int32_t* __restric
           fold_in<DT, OP>(acc, t1);
         }
         if (j < L) fold_in<DT, OP>(acc, row(buf[j]));
+      } else if constexpr (ORDERED) {
+        // L, v - sub and so every trip count below are the same in all lanes of the group
+        int32_t prev = -1;                               // the largest row index combined so far
+        for (int done = 0; done < L; done += kOrderMax) {
+          const int cnt = L - done < kOrderMax ? L - done : kOrderMax;
+          wave_lds_sync();                               // the group has read the previous batch
+          if (sub == 0) {
+            int have = 0, s = 0;
+            for (int32_t i = rhead[u]; i >= 0 && s < L; i = next[i], ++s) {
+              if (i <= prev || (have == kOrderMax && i > buf[kOrderMax - 1])) continue;
+              int b = (have < kOrderMax ? have : kOrderMax - 1) - 1;
+              while (b >= 0 && buf[b] > i) {
+                buf[b + 1] = buf[b];
+                --b;
+              }
+              buf[b + 1] = i;
+              if (have < kOrderMax) ++have;
+            }
+          }
+          wave_lds_sync();
+          int j = 0;
+          if (done == 0) unpack<DT>(row(buf[j++]), acc);
+          for (; j < cnt; ++j) fold_in<DT, OP>(acc, row(buf[j]));
+          prev = buf[cnt - 1];
+        }
       } else {
         int32_t i = rhead[u];
         unpack<DT>(row(i), acc);
@@ -325,6 +430,17 @@ __global__ __launch_bounds__(kBlock) void k_dense_compact(const unsigned long lo
     m_flag[0] = (unsigned long long)(tile_base[ntiles - 1] + tile_cnt[ntiles - 1]);
 }
 
+// K5c: the side run of rows keyed -1, if any, becomes the last run.  One lane, after
+// k_dense_compact has written m_flag[0]: no atomic on the run counter.
+__global__ void k_hashc_side(const SideRun* __restrict__ side, int64_t* __restrict__ out_keys,
+                             int32_t* __restrict__ rhead, unsigned long long* __restrict__ m_flag) {
+  if (blockIdx.x != 0 || threadIdx.x != 0 || side->head < 0) return;
+  const unsigned long long u = m_flag[0];
+  out_keys[u] = -1;
+  rhead[u] = side->head;
+  m_flag[0] = u + 1;
+}
+
 // Keys only (set operations): every run's row count, one lane per run walking its list.
 __global__ __launch_bounds__(kBlock) void k_run_counts(const int32_t* __restrict__ rhead,
                                                        const int32_t* __restrict__ next,
@@ -337,12 +453,6 @@ __global__ __launch_bounds__(kBlock) void k_run_counts(const int32_t* __restrict
     for (int32_t i = rhead[u]; i >= 0; i = next[i]) ++L;
     out_count[u] = L;
   }
-}
-
-int64_t table_slots(int64_t n) {
-  int64_t t = 1024;
-  while (t < 2 * n) t <<= 1;
-  return t;
 }
 
 size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
@@ -367,7 +477,7 @@ Layout layout(int64_t n) {
   return L;
 }
 
-template <int DT, int OP>
+template <int DT, int OP, bool ORDERED>
 int launch_reduce(const int32_t* rhead, const int32_t* next, const unsigned long long* m_dev, int64_t n,
                   const void* vals, int64_t dim, void* out, int32_t* out_count, hipStream_t st) {
   using S = typename Elem<DT>::S;
@@ -378,21 +488,25 @@ int launch_reduce(const int32_t* rhead, const int32_t* next, const unsigned long
   while (G < units && G < 64) G <<= 1;
   const int g = grid_for((n * G + 63) / 64 * 64, 1);
   if (vec)
-    hipLaunchKernelGGL((k_hash_reduce<DT, OP, true>), dim3(g), dim3(kBlock), 0, st, rhead, next, m_dev, vals, units,
+    hipLaunchKernelGGL((k_hash_reduce<DT, OP, true, ORDERED>), dim3(g), dim3(kBlock), 0, st, rhead, next, m_dev, vals, units,
                        G, out, out_count);
   else
-    hipLaunchKernelGGL((k_hash_reduce<DT, OP, false>), dim3(g), dim3(kBlock), 0, st, rhead, next, m_dev, vals, units,
+    hipLaunchKernelGGL((k_hash_reduce<DT, OP, false, ORDERED>), dim3(g), dim3(kBlock), 0, st, rhead, next, m_dev, vals, units,
                        G, out, out_count);
   return (int)hipGetLastError();
 }
 
-// The reduce launch of both entry points (hash and dense), for a runtime (dtype, op).
+// The reduce launch of the entry points (hash, dense, canonical), for a runtime (dtype, op).
+// ``ordered``: runs longer than kOrderMax rows combine in input order too (K5c).
 int reduce_runs(int dtype, int op, const int32_t* rhead, const int32_t* next, const unsigned long long* m_dev,
-                int64_t n, const void* vals, int64_t dim, void* out, int32_t* out_count, hipStream_t st) {
+                int64_t n, const void* vals, int64_t dim, void* out, int32_t* out_count, hipStream_t st,
+                bool ordered = false) {
   return with_dtype(dtype, [&](auto dtc) {
     constexpr int DT = decltype(dtc)::value;
     return with_op_of<DT>(RowOps{}, op, MP4X_E_UNSUPPORTED, [&](auto opc) {
-      return launch_reduce<DT, decltype(opc)::value>(rhead, next, m_dev, n, vals, dim, out, out_count, st);
+      constexpr int OP = decltype(opc)::value;
+      if (ordered) return launch_reduce<DT, OP, true>(rhead, next, m_dev, n, vals, dim, out, out_count, st);
+      return launch_reduce<DT, OP, false>(rhead, next, m_dev, n, vals, dim, out, out_count, st);
     });
   });
 }
@@ -423,6 +537,25 @@ DenseLayout dense_layout(int64_t n, int64_t T) {
                                 (size_t)(L.ntiles < 1 ? 1 : L.ntiles), rocprim::plus<int64_t>(), (hipStream_t)0);
   L.temp = o;   o += align256(L.temp_bytes);
   L.total = o;
+  return L;
+}
+
+// K5c's scratch: the dense layout over T = table_slots(n) slots (table keys, slot list heads,
+// next[row], run list heads, the tile counts and bases, the scan's temporary), then the side run.
+struct CanonLayout {
+  DenseLayout d;
+  size_t side, total;
+  int64_t t;
+};
+
+CanonLayout canon_layout(int64_t n) {
+  CanonLayout L;
+  L.t = table_slots(n);
+  L.d = dense_layout(n, L.t);
+  // (the dense layout's min(n, T) = n run list heads suffice: n rows give at most n runs, the side
+  // run among them)
+  L.side = L.d.total;
+  L.total = L.side + 256;
   return L;
 }
 }  // namespace
@@ -503,4 +636,44 @@ extern "C" int mp4x_dense_reduce_by_key(int dtype, int op, const int64_t* keys, 
     return (int)hipGetLastError();
   }
   return reduce_runs(dtype, op, rhead, next, m_dev, n, vals, dim, out_vals, out_count, st);
+}
+
+extern "C" size_t mp4x_hash_rbk_canonical_scratch_bytes(int64_t n) { return canon_layout(n < 0 ? 0 : n).total; }
+
+// K5c: init, priority insert, link (the table is final), ordered compaction over the table's slots
+// (K5d's count / scan / compact), the side run last, the reduce with every run in input order.
+extern "C" int mp4x_hash_reduce_by_key_canonical(int dtype, int op, const int64_t* keys, int64_t n, const void* vals,
+                                                 int64_t dim, void* scratch, size_t scratch_bytes, int64_t* out_keys,
+                                                 void* out_vals, int32_t* out_count, int64_t* m_flag, void* stream) {
+  if (!mp4x_hash_rbk_supported(dtype, op) || n < 0 || dim <= 0 || n >= (1ll << 30)) return MP4X_E_UNSUPPORTED;
+  const CanonLayout L = canon_layout(n);
+  if (scratch_bytes < L.total || ((uintptr_t)scratch & 255) || ((uintptr_t)m_flag & 7)) return MP4X_E_BADARG;
+  hipStream_t st = (hipStream_t)stream;
+  char* p = (char*)scratch;
+  auto* tkeys = (unsigned long long*)(p + L.d.tkeys);
+  auto* thead = (int32_t*)(p + L.d.thead);
+  auto* next = (int32_t*)(p + L.d.next);
+  auto* rhead = (int32_t*)(p + L.d.rhead);
+  auto* tcnt = (int64_t*)(p + L.d.tcnt);
+  auto* tbase = (int64_t*)(p + L.d.tbase);
+  auto* side = (SideRun*)(p + L.side);
+  auto* flag = (unsigned long long*)m_flag;
+  const uint64_t mask = (uint64_t)(L.t - 1);
+  hipLaunchKernelGGL(k_hash_init, dim3(grid_for(L.t, 2)), dim3(kBlock), 0, st, tkeys, thead, L.t, side, flag);
+  if (n == 0) return (int)hipGetLastError();
+  hipLaunchKernelGGL(k_hashc_insert, dim3(grid_for(n, 1)), dim3(kBlock), 0, st, keys, n, tkeys, mask,
+                     hmap::advance_bound(L.t), hmap::iter_bound(n, L.t), flag);
+  hipLaunchKernelGGL(k_hashc_link, dim3(grid_for(n, 1)), dim3(kBlock), 0, st, keys, n,
+                     (const unsigned long long*)tkeys, thead, mask, hmap::advance_bound(L.t), next, side, flag);
+  hipLaunchKernelGGL(k_dense_count, dim3((unsigned)L.d.ntiles), dim3(kBlock), 0, st, (const int32_t*)thead, L.t, tcnt);
+  size_t tb = L.d.temp_bytes;
+  if (hipError_t e = rocprim::exclusive_scan(p + L.d.temp, tb, (const int64_t*)tcnt, tbase, (int64_t)0,
+                                             (size_t)L.d.ntiles, rocprim::plus<int64_t>(), st))
+    return (int)e;
+  hipLaunchKernelGGL(k_dense_compact, dim3((unsigned)L.d.ntiles), dim3(kBlock), 0, st,
+                     (const unsigned long long*)tkeys, (const int32_t*)thead, L.t, (const int64_t*)tbase,
+                     (const int64_t*)tcnt, L.d.ntiles, out_keys, rhead, flag);
+  hipLaunchKernelGGL(k_hashc_side, dim3(1), dim3(64), 0, st, (const SideRun*)side, out_keys, rhead, flag);
+  if (int e = (int)hipGetLastError()) return e;
+  return reduce_runs(dtype, op, rhead, next, flag, n, vals, dim, out_vals, out_count, st, true);
 }

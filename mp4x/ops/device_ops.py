@@ -1089,6 +1089,45 @@ def hash_reduce_by_key(keys: torch.Tensor, vals: torch.Tensor, op: int, stream=N
     return out_keys[:m], out_vals[:m], out_count[:m]
 
 
+def hash_reduce_by_key_canonical(keys: torch.Tensor, vals: torch.Tensor, op: int, stream=None):
+    """K5c (csrc/kernels/sparse_hash.hip): the hash reduce-by-key whose result is a function of its
+    input alone — (unique_keys, reduced_rows, counts) in CANONICAL TABLE order: the occupied slots,
+    in slot order, of the table that plain linear probing builds from the distinct keys in
+    ascending unsigned order (``table_slots(n)`` slots, splitmix64 homes; the definition in torch:
+    :func:`mp4x.parallel.sparse.canonical_rbk_torch`), then the run of rows keyed -1, if any.
+    Every key's rows combine in input order whatever their number: the values and counts of
+    :func:`reduce_by_key`, bit for bit.  The same (dtype, op) pairs as :func:`hash_reduce_by_key`.
+
+    The kernels bound every loop; should a lane pass a bound (it cannot with a sound table), the
+    call falls back to :func:`reduce_by_key` and the keys come back ASCENDING instead."""
+    _dev_check(keys, vals)
+    n = keys.numel()
+    if keys.dtype != torch.int64 or vals.dim() not in (1, 2) or vals.shape[0] != n:
+        raise ValueError("hash_reduce_by_key_canonical: int64 keys[n] and vals[n] / vals[n, dim]")
+    if not hash_rbk_supported(vals.dtype, op):
+        raise ValueError(f"hash_reduce_by_key_canonical: {vals.dtype} op {op} not supported")
+    dev = keys.device
+    dim = 1 if vals.dim() == 1 else int(vals.shape[1])
+    keys, vals = keys.contiguous(), vals.contiguous()
+    lib = native.hip()
+    sb = lib.mp4x_hash_rbk_canonical_scratch_bytes(n)
+    scratch = torch.empty(sb + 256, dtype=torch.uint8, device=dev)
+    sp = scratch.data_ptr()
+    sp += (-sp) % 256                                       # the native layout is 256-byte aligned
+    m_flag = torch.empty(2, dtype=torch.int64, device=dev)
+    out_keys = torch.empty(n, dtype=torch.int64, device=dev)
+    out_vals = torch.empty_like(vals)
+    out_count = torch.empty(n, dtype=torch.int32, device=dev)
+    check(lib.mp4x_hash_reduce_by_key_canonical(int(dtype_of_torch(vals.dtype)), int(op), keys.data_ptr(), n,
+                                                vals.data_ptr(), dim, sp, sb, out_keys.data_ptr(),
+                                                out_vals.data_ptr(), out_count.data_ptr(), m_flag.data_ptr(),
+                                                stream_ptr(stream)), "mp4x_hash_reduce_by_key_canonical")
+    m, bad = m_flag.tolist()                                # one sync for both
+    if bad:
+        return reduce_by_key(keys, vals, int(op), stream=stream)
+    return out_keys[:m], out_vals[:m], out_count[:m]
+
+
 def dense_reduce_by_key(keys: torch.Tensor, vals: Optional[torch.Tensor], op: int, base: int, stride: int, T: int,
                         stream=None):
     """K5d (csrc/kernels/sparse_hash.hip): reduce-by-key of DENSE keys — ``k // stride - base`` in

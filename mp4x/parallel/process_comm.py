@@ -871,28 +871,48 @@ class ProcessCommSlave:
             raise Mp4jException(f"keys outside [0, 2**{keyBits}) with keyBits={keyBits}")
         return keyBits
 
-    def allreduceSparse(self, keys, vals, operator, keyBits: Optional[int] = None):
+    @staticmethod
+    def _check_key_order(keyOrder):
+        from .sparse import KEY_ORDERS
+        if keyOrder not in KEY_ORDERS:
+            raise Mp4jException(f"keyOrder {keyOrder!r}: one of {KEY_ORDERS}")
+        return keyOrder
+
+    def allreduceSparse(self, keys, vals, operator, keyBits: Optional[int] = None, keyOrder: str = "ascending"):
         """Sparse allreduce of (int64 id, value-row) pairs on the device engine (extension).
 
         Every rank returns ``(keys, vals)`` holding the op-reduction over all ranks of the rows
         sharing an id (the tensor form of ``allreduceMap`` for ``Map<String, float[]>``).
         ``keyBits``: ids are known to lie in [0, 2**keyBits) (e.g. embedding rows), so the
         reduce-by-key radix sort covers only those bits.
+        ``keyOrder``: "ascending" (the default: every owner's keys ascending) or "table": the owners
+        reduce by hashing instead of sorting (K5c) and the result is still the same on every run
+        and every rank, a function of the call's inputs — per owner the keys ascending where the
+        ids are dense enough for direct addressing (K5d), else in the order of the canonical hash
+        table of the owner's keys; the values are those of "ascending", bit for bit.  Custom
+        operators and (dtype, op) pairs without a hash kernel keep the sort.  Any other value is
+        refused before the call counts.
         """
+        self._check_key_order(keyOrder)
         self._tick("allreduceSparse")
         if self.slaveNum == 1:
             return keys, vals
         from .sparse import allreduce_sparse
-        return allreduce_sparse(self.device, keys, vals, operator, self._check_key_bits(keys, keyBits))
+        return allreduce_sparse(self.device, keys, vals, operator, self._check_key_bits(keys, keyBits), keyOrder)
 
-    def reduceSparse(self, keys, vals, operator, rootRank: int, keyBits: Optional[int] = None):
-        """Tensor form of ``reduceMap``: root gets the op-reduced union (others: their owned share)."""
+    def reduceSparse(self, keys, vals, operator, rootRank: int, keyBits: Optional[int] = None,
+                     keyOrder: str = "ascending"):
+        """Tensor form of ``reduceMap``: root gets the op-reduced union (others: their owned share).
+        ``keyOrder``: as in :meth:`allreduceSparse`, for the owners' reduce-by-key (the root's merge
+        sorts the union: its keys are ascending either way)."""
+        self._check_key_order(keyOrder)
         self._tick("reduceSparse")
         if self.slaveNum == 1:
             return keys, vals
         self._check_root(rootRank)
         from .sparse import reduce_sparse
-        return reduce_sparse(self.device, keys, vals, operator, rootRank, self._check_key_bits(keys, keyBits))
+        return reduce_sparse(self.device, keys, vals, operator, rootRank, self._check_key_bits(keys, keyBits),
+                             keyOrder)
 
     def gatherSparse(self, keys, vals, rootRank: int):
         """Tensor form of ``gatherMap``: union at root, duplicate ids keep the lowest rank's row (K8)."""

@@ -160,12 +160,81 @@ def _sync_new_keys(engine, new: List) -> None:
 # csrc/kernels/sparse_hash.hip: open addressing, a row list per key, rows combined in input order —
 # the same values bit for bit, 1.4-1.6x faster on config 4's owner rows; keys in table order,
 # which depends on the CAS races of colliding keys).  A/B: profiles/r6/sparse/v3_*.
+# "hashc" (K5c: the hash path made canonical — K5d where the dense plan holds, else the keys in the
+# order of the canonical table, a function of the key set; every run combined in input order) is
+# what ``keyOrder="table"`` asks for per call.  A/B: profiles/r23/sparse_hashc/.
 RBK_MODE = os.environ.get("MP4X_SPARSE_RBK", "sort").lower()
+KEY_ORDERS = ("ascending", "table")
+
+
+def check_key_order(key_order: str) -> str:
+    """``keyOrder`` of the sparse tensor collectives: "ascending" (per owner; the default) or
+    "table" (per owner K5d's ascending order where the dense plan holds, else the canonical
+    table's: the same on every run and every rank, a function of the call's inputs)."""
+    if key_order not in KEY_ORDERS:
+        raise ValueError(f"keyOrder {key_order!r}: one of {KEY_ORDERS}")
+    return key_order
+
+
+_SPLITMIX = (0xbf58476d1ce4e5b9, 0x94d049bb133111eb)
+
+
+def _table_slots(n: int) -> int:
+    t = 1024
+    while t < 2 * n:
+        t <<= 1
+    return t
+
+
+def canonical_table_order(ukeys: np.ndarray, n: int) -> np.ndarray:
+    """The positions of ``ukeys`` (distinct int64 keys other than -1, in ascending UNSIGNED order)
+    listed by ascending slot of the canonical table of an ``n``-row reduce-by-key
+    (csrc/kernels/sparse_hash_map.hpp): t = the smallest power of two >= max(1024, 2n) slots,
+    home = splitmix64(key) & (t - 1), the keys inserted in the given order by plain linear
+    probing."""
+    t = _table_slots(n)
+    k = ukeys.astype(np.uint64)
+    with np.errstate(over="ignore"):
+        k = k ^ (k >> np.uint64(30))
+        k = k * np.uint64(_SPLITMIX[0])
+        k = k ^ (k >> np.uint64(27))
+        k = k * np.uint64(_SPLITMIX[1])
+        k = k ^ (k >> np.uint64(31))
+    homes = (k & np.uint64(t - 1)).astype(np.int64).tolist()
+    slot_of = [0] * len(homes)
+    taken = bytearray(t)
+    for j, h in enumerate(homes):
+        while taken[h]:
+            h = (h + 1) & (t - 1)
+        taken[h] = 1
+        slot_of[j] = h
+    return np.argsort(np.asarray(slot_of, dtype=np.int64), kind="stable")
+
+
+def canonical_rbk_torch(keys: torch.Tensor, vals: torch.Tensor, op):
+    """K5c's definition in torch / numpy, and the CPU path of ``keyOrder="table"``: (unique_keys,
+    reduced_rows, counts) with the keys in canonical table order (the run of key -1 last) and every
+    key's rows combined by ``op`` (an operator object) in input order — the values and counts of
+    the ascending path, reordered."""
+    keys = keys.cpu()
+    uk, uv, cnt = _rbk_cpu(keys, vals.cpu(), op)                     # ascending (signed), input order
+    uk_np = uk.numpy()
+    real = np.flatnonzero(uk_np != -1)
+    real = real[np.argsort(uk_np[real].astype(np.uint64), kind="stable")]     # ascending unsigned
+    order = real[canonical_table_order(uk_np[real], int(keys.numel()))]
+    order = torch.from_numpy(np.concatenate([order, np.flatnonzero(uk_np == -1)]))
+    return uk[order], uv[order], cnt[order]
+
+
 def _reduce_by_key(keys: torch.Tensor, vals: Optional[torch.Tensor], op, key_bits: Optional[int] = None,
-                   dense=None):
+                   dense=None, key_order: str = "ascending"):
     """``key_bits``: every key is in [0, 2**key_bits) (dense dictionary ids) — the radix sort
     covers those bits only.  ``dense`` = (base, stride, T) from :func:`_dense_plan`: K5d runs
-    instead (no sort; the same result, order included) unless the keys turn out not dense."""
+    instead (no sort; the same result, order included) unless the keys turn out not dense.
+    ``key_order`` "table" (or ``MP4X_SPARSE_RBK=hashc``): K5c instead of the sort where K5d does
+    not apply (not for keys only, custom operators or (dtype, op) pairs the hash paths lack)."""
+    table = (key_order == "table" or RBK_MODE == "hashc") and vals is not None and \
+        not getattr(op, "is_custom", False)
     if keys.is_cuda:
         from ..ops.device_ops import reduce_by_key
         if dense is not None and RBK_MODE != "hash" and (vals is None or not getattr(op, "is_custom", False)):
@@ -178,8 +247,17 @@ def _reduce_by_key(keys: torch.Tensor, vals: Optional[torch.Tensor], op, key_bit
             from ..ops.device_ops import hash_rbk_supported, hash_reduce_by_key
             if hash_rbk_supported(vals.dtype, int(op.code)):
                 return hash_reduce_by_key(keys, vals, int(op.code))
+        if table and RBK_MODE != "hash":
+            from ..ops.device_ops import hash_rbk_supported, hash_reduce_by_key_canonical
+            if hash_rbk_supported(vals.dtype, int(op.code)):
+                return hash_reduce_by_key_canonical(keys, vals, int(op.code))
         return reduce_by_key(keys, vals, int(op.code) if vals is not None else 0, key_bits=key_bits)
-    # CPU twin for the gloo test configuration only
+    return canonical_rbk_torch(keys, vals, op) if table else _rbk_cpu(keys, vals, op)
+
+
+def _rbk_cpu(keys: torch.Tensor, vals: Optional[torch.Tensor], op):
+    """CPU twin of the sort path, for the gloo test configuration only: keys ascending, every key's
+    rows combined in input order."""
     uk, inv, cnt = torch.unique(keys, sorted=True, return_inverse=True, return_counts=True)
     if vals is None:
         return uk, None, cnt.to(torch.int32)
@@ -553,17 +631,22 @@ def _allgather_v(engine, t: torch.Tensor, sizes: Optional[List[int]] = None) -> 
     return torch.cat([gath[i * m:i * m + s] for i, s in enumerate(sizes)], 0)
 
 
-def allreduce_sparse(engine, keys: torch.Tensor, vals: torch.Tensor, operator, key_bits: Optional[int] = None):
+def allreduce_sparse(engine, keys: torch.Tensor, vals: torch.Tensor, operator, key_bits: Optional[int] = None,
+                     key_order: str = "ascending"):
     """All ranks end with the op-reduction of every rank's (key, row) pairs, keys ascending per owner.
 
-    ``keys`` int64 [n] (unique per rank), ``vals`` [n, dim] (or [n]).
+    ``keys`` int64 [n] (unique per rank), ``vals`` [n, dim] (or [n]).  ``key_order`` "table": per
+    owner the keys come in K5d's ascending order where the dense plan holds, else in the canonical
+    table's order (K5c) — the same tensors on every run and every rank, and no radix sort; nothing
+    downstream (the all-gather of the owners' pieces) looks at the order.
     """
+    check_key_order(key_order)
     squeeze = vals.dim() == 1
     v2 = vals.view(-1, 1) if squeeze else vals
     op = operator if getattr(operator, "is_custom", False) else for_dtype(operator, dtype_of_torch(vals.dtype))
     rkeys, rvals, rng = _exchange_by_owner(engine, keys, v2)
     uk, uv, _ = _reduce_by_key(rkeys, rvals, op, key_bits or (rng.bits if rng else None),
-                               _dense_plan(rng or _bits_range(key_bits), engine.p, rkeys))
+                               _dense_plan(rng or _bits_range(key_bits), engine.p, rkeys), key_order)
     sizes = _row_counts(engine, uk.shape[0], uk.device)     # one count round for keys AND rows
     got = _ipc_allgatherv(engine, uk, uv, sizes) if _sparse_ipc_ok(engine, uk) else None
     if got is not None:
@@ -644,14 +727,17 @@ def broadcast_sparse(engine, keys: Optional[torch.Tensor], vals: Optional[torch.
 
 
 def reduce_sparse(engine, keys: torch.Tensor, vals: torch.Tensor, operator, root: int,
-                  key_bits: Optional[int] = None):
-    """Owner exchange + K5 reduce-by-key, then the owner-disjoint pieces go to ``root``."""
+                  key_bits: Optional[int] = None, key_order: str = "ascending"):
+    """Owner exchange + K5 reduce-by-key, then the owner-disjoint pieces go to ``root``.
+    ``key_order``: as in :func:`allreduce_sparse`, for the owners' pieces (what the other ranks
+    return); the root's merge (K8) sorts the union, so the root's keys are ascending either way."""
+    check_key_order(key_order)
     squeeze = vals.dim() == 1
     v2 = vals.view(-1, 1) if squeeze else vals
     op = operator if getattr(operator, "is_custom", False) else for_dtype(operator, dtype_of_torch(vals.dtype))
     rkeys, rvals, rng = _exchange_by_owner(engine, keys, v2)
     uk, uv, _ = _reduce_by_key(rkeys, rvals, op, key_bits or (rng.bits if rng else None),
-                               _dense_plan(rng or _bits_range(key_bits), engine.p, rkeys))
+                               _dense_plan(rng or _bits_range(key_bits), engine.p, rkeys), key_order)
     gk, gv = gather_sparse(engine, uk, uv, root, key_bits)    # disjoint owners: K8 dedupe is a no-op
     return gk, (gv.view(-1) if squeeze else gv)
 
