@@ -14,6 +14,7 @@ import pytest
 torch = pytest.importorskip("torch")
 
 from spawn_ranks import run_spawn  # noqa: E402
+from vmm_support import require_peer_vmm_import  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -60,6 +61,7 @@ def _alloc_allreduce_fn(comm, n, reps):
 
 
 def test_memalloc_above_2gib_zero_copy_exact():
+    require_peer_vmm_import()
     n = (2 << 30) // 4 + (1 << 20)            # 2 GiB + 4 MiB of float32
     out = run_spawn(2, _alloc_allreduce_fn, args=(n, 2), timeout=300)
     for r, (bad, used, info, ok2) in out.items():
@@ -70,6 +72,7 @@ def test_memalloc_above_2gib_zero_copy_exact():
 
 
 def test_memalloc_many_chunks():
+    require_peer_vmm_import()
     n = (40 << 20) // 4 + 16                    # 40 MiB + 64 B over 8 MiB chunks: 6 chunks
     out = run_spawn(3, _alloc_allreduce_fn, args=(n, 2), env={"MP4X_VMM_CHUNK": str(8 << 20)})
     for r, (bad, used, info, ok2) in out.items():
@@ -131,6 +134,7 @@ def _fp8_whole_fn(comm, n):
 
 
 def test_fp8_whole_tensor_staging_built_from_vmm():
+    require_peer_vmm_import()
     # the open limit lowered to 64 MiB so a ~85 MB quantised tensor needs the VMM-built staging
     # buffer (the path BASELINE config 5, 8 GB of f32 -> 2 GB of e4m3, takes at the real limit)
     n = 80 << 20

@@ -20,6 +20,7 @@ import pytest
 torch = pytest.importorskip("torch")
 
 from spawn_ranks import run_spawn  # noqa: E402
+from vmm_support import require_peer_vmm_import  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -76,6 +77,8 @@ def _note(row):
 @pytest.mark.parametrize("policy", ["chunks", "fresh_va", "hint", "keep_owner_va", "keep_import_va", "ordered", "pool"])
 def test_memfree_policy(policy):
     from mp4x.parallel import ipc as ipc_mod
+    if policy in (ipc_mod.VMM_POLICY, "pool", "fresh_va"):
+        require_peer_vmm_import()           # the asserted rows are about peer-mapped memory
     env = {"MP4X_VMM_POLICY": policy, "MP4X_IPC_SELFTEST": "0"}
     out = run_spawn(2, _policy_fn, env=env, timeout=200)
     _note({"policy": policy, "ranks": out})
