@@ -342,6 +342,37 @@ int mp4x_moe_priority_mask(const void* ids, int ids_are_i64, const float* priori
                            const int64_t* limit_vec, const void* route_scratch, size_t route_scratch_bytes,
                            void* out_ids, int64_t* masked, void* scratch, size_t scratch_bytes, void* stream);
 
+// ---------------------------------------------------------------- K16 GBDT in exact fixed point
+// gh[r] = (q(g[r], shift_g), q(h[r], shift_h)) for r < n, int32 pairs: q(x, s) = rint(f64(x) * 2^s),
+// half to even (the product is exact), NaN -> 0, clamped to +-(2^31 - 1).  g, h f32[n] 8-byte aligned,
+// gh 16-byte aligned, |shift| <= 200, 0 <= n < 2^31, else MP4X_E_BADARG; n == 0 launches nothing.
+int mp4x_gbdt_quantize(const float* g, const float* h, int64_t n, int shift_g, int shift_h, int32_t* gh, void* stream);
+// hist[j, f, b] = the int64 sums of gh[r] over the row slots node j owns with bins[r, f] == b.  bins
+// u8[n, F] row-major (no alignment is assumed, F >= 1), gh int32[n, 2], rows int32[m] (a row index
+// outside [0, n) is skipped), seg int64[k + 1] in device memory: node j owns the slots [c[j], c[j+1])
+// of rows with c[0] = 0, c[j+1] = max(c[j], min(seg[j+1], m)) - any table is legal, it is read once on
+// the device and clamped (csrc/kernels/gbdt_hist_map.hpp).  A bin value >= B is skipped.  2 <= B <=
+// 256, 0 <= k <= 4096, n, m < 2^31.  hist int64[k, F, B, 2] is zeroed first, on the same stream, then
+// filled with integer atomics only: the same bits whatever the schedule.  scratch: 4-byte aligned,
+// mp4x_gbdt_hist_scratch_bytes(k) bytes (0 for a k the call refuses).  Bad sizes, null or misaligned
+// pointers are MP4X_E_BADARG before any launch; k == 0 launches nothing, m == 0 or n == 0 only zeroes.
+size_t mp4x_gbdt_hist_scratch_bytes(int k);
+int mp4x_gbdt_hist(const uint8_t* bins, const int32_t* gh, const int32_t* rows, const int64_t* seg, int64_t n, int64_t F,
+                   int B, int64_t m, int k, int64_t* hist, void* scratch, size_t scratch_bytes, void* stream);
+// The best split of every node of hist int64[k, F, B, 2].  Per feature the inclusive int64 prefix
+// sums GL, HL over the bins, G, H the feature's last prefix; in f64 with x = int * 2^-shift,
+// gain(f, t) = GL^2 / (HL + lam) + GR^2 / (HR + lam) - G^2 / (H + lam) for t in [0, B - 2], GR = G - GL
+// and HR = H - HL in int64; the operations in that order, each rounded once, no contraction.  The
+// largest finite gain wins, ties to the lower f, then the lower t; a NaN or infinite gain never
+// wins.  gain[j] is the winner's (-inf: no finite gain); feature[j] = threshold[j] = -1 and GL = HL = 0
+// when the gain is <= 1e-12 or not finite; G, H are the winning feature's, feature 0's without one.
+// Outputs [k], 8-byte aligned (feature, threshold int32: 4); scratch 8-byte aligned,
+// mp4x_gbdt_split_scratch_bytes(k, F) bytes.  k == 0 launches nothing.
+size_t mp4x_gbdt_split_scratch_bytes(int64_t k, int64_t F);
+int mp4x_gbdt_split(const int64_t* hist, int64_t k, int64_t F, int B, int shift_g, int shift_h, double lam, double* gain,
+                    int32_t* feature, int32_t* threshold, int64_t* GL, int64_t* HL, int64_t* G, int64_t* H,
+                    void* scratch, size_t scratch_bytes, void* stream);
+
 // ---------------------------------------------------------------- errors
 // Reads and clears this thread's last HIP error.  mp4x reports its own failures through return
 // codes; a failed HIP call must not stay "last error" for PyTorch's next kernel-launch check to

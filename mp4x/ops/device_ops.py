@@ -683,6 +683,111 @@ def moe_priority_mask(rc: RouteCount, priority: torch.Tensor, limit, out: Option
     return out, masked
 
 
+GBDT_MAX_NODES = 4096                # csrc/kernels/gbdt_hist_map.hpp: kMaxNodes
+GBDT_MAX_SHIFT = 200
+
+
+def _gbdt_shift(fn: str, *shifts) -> None:
+    for s in shifts:
+        if isinstance(s, bool) or not isinstance(s, int) or abs(s) > GBDT_MAX_SHIFT:
+            raise ValueError(f"{fn}: the shift {s!r} is not an int in [-{GBDT_MAX_SHIFT}, {GBDT_MAX_SHIFT}]")
+
+
+def _gbdt_out(fn: str, out: Optional[torch.Tensor], shape, dtype, device) -> torch.Tensor:
+    if out is None:
+        return torch.empty(shape, dtype=dtype, device=device)
+    if out.dtype != dtype or tuple(out.shape) != tuple(shape) or out.device != device or not out.is_contiguous():
+        raise ValueError(f"{fn}: out must be a contiguous {dtype} {list(shape)} on {device}")
+    return out
+
+
+def gbdt_quantize(g: torch.Tensor, h: torch.Tensor, sg: int, sh: int, out: Optional[torch.Tensor] = None,
+                  stream=None) -> torch.Tensor:
+    """K16: ``gh`` int32 ``[n, 2]`` with ``gh[r] = (q(g[r], sg), q(h[r], sh))``, ``q(x, s) =
+    rint(float64(x) * 2**s)`` (half to even), NaN -> 0, clamped to ``+-(2**31 - 1)``; ``g``, ``h``
+    float32 ``[n]``."""
+    _dev_check(g, h, out)
+    _gbdt_shift("gbdt_quantize", sg, sh)
+    n = g.numel()
+    if g.dtype != torch.float32 or h.dtype != torch.float32 or g.dim() != 1 or tuple(h.shape) != (n,):
+        raise ValueError("gbdt_quantize: g and h must be float32 [n]")
+    if n >= 2 ** 31 or g.data_ptr() & 7 or h.data_ptr() & 7:
+        raise ValueError("gbdt_quantize: n must be below 2**31 and g, h 8-byte aligned")
+    out = _gbdt_out("gbdt_quantize", out, (n, 2), torch.int32, g.device)
+    if n and out.data_ptr() & 15:
+        raise ValueError("gbdt_quantize: out must be 16-byte aligned")
+    check(native.hip().mp4x_gbdt_quantize(g.data_ptr() if n else None, h.data_ptr() if n else None, n, sg, sh,
+                                          out.data_ptr() if n else None, stream_ptr(stream)), "mp4x_gbdt_quantize")
+    return out
+
+
+def gbdt_histogram(bins: torch.Tensor, gh: torch.Tensor, rows: torch.Tensor, seg: torch.Tensor, B: int,
+                   out: Optional[torch.Tensor] = None, stream=None) -> torch.Tensor:
+    """K16: ``hist`` int64 ``[k, F, B, 2]``, ``hist[j, f, b] = sum gh[r]`` over the rows node j owns
+    with ``bins[r, f] == b``.  ``bins`` uint8 ``[n, F]``, ``gh`` int32 ``[n, 2]``, ``rows`` int32 ``[m]``
+    (an index outside ``[0, n)`` is skipped), ``seg`` int64 ``[k + 1]`` on the device: node j owns
+    ``rows[c[j]:c[j+1]]``, ``c[0] = 0``, ``c[j+1] = max(c[j], min(seg[j+1], m))``; the table is read on the
+    device only, any content is legal.  A bin value ``>= B`` is skipped.  Integer atomics only: the same
+    bits run to run.  ``out`` is zeroed by the call."""
+    _dev_check(bins, gh, rows, seg, out)
+    if isinstance(B, bool) or not isinstance(B, int) or not 2 <= B <= 256:
+        raise ValueError(f"gbdt_histogram: B {B!r} must be an int in [2, 256]")
+    if bins.dtype != torch.uint8 or bins.dim() != 2 or bins.shape[1] < 1:
+        raise ValueError("gbdt_histogram: bins must be uint8 [n, F] with F >= 1")
+    n, F = bins.shape
+    if gh.dtype != torch.int32 or tuple(gh.shape) != (n, 2):
+        raise ValueError(f"gbdt_histogram: gh must be int32 [{n}, 2]")
+    if rows.dtype != torch.int32 or rows.dim() != 1 or seg.dtype != torch.int64 or seg.dim() != 1 or seg.numel() < 1:
+        raise ValueError("gbdt_histogram: rows must be int32 [m] and seg int64 [k + 1]")
+    m, k = rows.numel(), seg.numel() - 1
+    if n >= 2 ** 31 or m >= 2 ** 31 or k > GBDT_MAX_NODES or k * F * B >= 2 ** 31:
+        raise ValueError(f"gbdt_histogram: n, m and k * F * B must be below 2**31 and k at most {GBDT_MAX_NODES}")
+    out = _gbdt_out("gbdt_histogram", out, (k, F, B, 2), torch.int64, bins.device)
+    lib = native.hip()
+    sb = lib.mp4x_gbdt_hist_scratch_bytes(k)
+    scratch = torch.empty(max(sb, 4) // 4, dtype=torch.int32, device=bins.device)
+    check(lib.mp4x_gbdt_hist(bins.data_ptr() if n else None, gh.data_ptr() if n else None,
+                             rows.data_ptr() if m else None, seg.data_ptr(), n, F, B, m, k,
+                             out.data_ptr() if k else None, scratch.data_ptr(), sb, stream_ptr(stream)),
+          "mp4x_gbdt_hist")
+    return out
+
+
+class GbdtSplit(NamedTuple):
+    gain: torch.Tensor        # float64 [k]: the winner's gain, -inf without a finite one
+    feature: torch.Tensor     # int32 [k]: -1 when the gain is <= 1e-12 or not finite
+    threshold: torch.Tensor   # int32 [k]: go left if bin <= threshold
+    GL: torch.Tensor          # int64 [k]
+    HL: torch.Tensor
+    G: torch.Tensor           # the winning feature's totals, feature 0's without a winner
+    H: torch.Tensor
+
+
+def gbdt_best_split(hist: torch.Tensor, sg: int, sh: int, lam: float, out: Optional[GbdtSplit] = None,
+                    stream=None) -> GbdtSplit:
+    """K16: the best split of every node of ``hist`` int64 ``[k, F, B, 2]`` (the definition:
+    :func:`mp4x.parallel.gbdt.gbdt_split_torch`), float64 gains in the definition's order of
+    operations, ties to the lower feature, then the lower threshold."""
+    _dev_check(hist, *(out or ()))
+    _gbdt_shift("gbdt_best_split", sg, sh)
+    if hist.dtype != torch.int64 or hist.dim() != 4 or hist.shape[3] != 2 or hist.shape[1] < 1 or \
+            not 2 <= hist.shape[2] <= 256:
+        raise ValueError("gbdt_best_split: hist must be int64 [k, F, B, 2] with F >= 1 and 2 <= B <= 256")
+    k, F, B, _ = hist.shape
+    if k * F >= 2 ** 31:
+        raise ValueError("gbdt_best_split: k * F must be below 2**31")
+    dts = (torch.float64, torch.int32, torch.int32, torch.int64, torch.int64, torch.int64, torch.int64)
+    o = GbdtSplit(*(_gbdt_out("gbdt_best_split", out[i] if out is not None else None, (k,), dt, hist.device)
+                    for i, dt in enumerate(dts)))
+    lib = native.hip()
+    sb = lib.mp4x_gbdt_split_scratch_bytes(k, F)
+    scratch = torch.empty(max(sb, 8) // 8, dtype=torch.int64, device=hist.device)
+    check(lib.mp4x_gbdt_split(hist.data_ptr() if k else None, k, F, B, sg, sh, float(lam),
+                              *(t.data_ptr() if k else None for t in o), scratch.data_ptr(), sb, stream_ptr(stream)),
+          "mp4x_gbdt_split")
+    return o
+
+
 MOE_COMBINE_BWD_MAX_TOP_K = 16       # csrc/kernels/moe.hip: kMoeBwdMaxK
 
 
