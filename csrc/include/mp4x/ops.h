@@ -373,6 +373,32 @@ int mp4x_gbdt_split(const int64_t* hist, int64_t k, int64_t F, int B, int shift_
                     int32_t* feature, int32_t* threshold, int64_t* GL, int64_t* HL, int64_t* G, int64_t* H,
                     void* scratch, size_t scratch_bytes, void* stream);
 
+// ---------------------------------------------------------------- K17 GBDT level advance
+// Stable two-way partition of every segment of a K16 table.  bins u8[n, F], rows int32[m], seg
+// int64[k + 1] (clamped as in mp4x_gbdt_hist, any table is legal), feature, threshold, first_right
+// int32[k] (first_right may be null: all 0), all in device memory.  Node j splits iff 0 <= feature[j]
+// < F; the rows of a node that does not split and a slot whose row index is outside [0, n) are
+// dropped.  Row r of a splitting node goes right iff bins[r, feature[j]] > threshold[j] (any int32
+// threshold) and is "first" iff went_right == (first_right[j] != 0), else "second".  seg_out
+// int64[2k + 1], seg_out[0] = 0: segment j of rows_out holds node j's first rows, segment k + j its
+// second rows, in slot order (stable); rows_out int32[m], only rows_out[0 .. seg_out[2k]) is written,
+// every slot once.  No atomics and no block waits on another: the same bits run to run.  0 <= k <=
+// 2048, n, m < 2^31, F >= 1; scratch 16-byte aligned, mp4x_gbdt_partition_scratch_bytes(m, k) bytes
+// (0 for arguments the call refuses).  Bad sizes, null or misaligned pointers and rows_out
+// overlapping rows are MP4X_E_BADARG before any launch; k == 0, m == 0 or n == 0 writes only seg_out
+// (all zero) and needs no other pointer.
+size_t mp4x_gbdt_partition_scratch_bytes(int64_t m, int k);
+int mp4x_gbdt_partition(const uint8_t* bins, const int32_t* rows, const int64_t* seg, const int32_t* feature,
+                        const int32_t* threshold, const int32_t* first_right, int64_t n, int64_t F, int64_t m, int k,
+                        int32_t* rows_out, int64_t* seg_out, void* scratch, size_t scratch_bytes, void* stream);
+// Sibling subtraction: large[p] = parent[parent_of[p]] - small[p] in wrapping int64 for p < kp, over
+// `cells` (g, h) pairs a node (F * B).  parent int64[k, cells, 2], small and large int64[kp, cells, 2],
+// 16-byte aligned, parent_of int32[kp]; a parent_of[p] outside [0, k) reads a zero histogram.  large
+// may be small, it may not overlap parent.  0 <= k, kp <= 4096, 1 <= cells < 2^31, else
+// MP4X_E_BADARG; kp == 0 launches nothing.
+int mp4x_gbdt_hist_subtract(const int64_t* parent, const int64_t* small, const int32_t* parent_of, int k, int kp,
+                            int64_t cells, int64_t* large, void* stream);
+
 // ---------------------------------------------------------------- errors
 // Reads and clears this thread's last HIP error.  mp4x reports its own failures through return
 // codes; a failed HIP call must not stay "last error" for PyTorch's next kernel-launch check to

@@ -788,6 +788,63 @@ def gbdt_best_split(hist: torch.Tensor, sg: int, sh: int, lam: float, out: Optio
     return o
 
 
+GBDT_MAX_PARENTS = GBDT_MAX_NODES // 2    # csrc/kernels/gbdt_part_map.hpp: kMaxParents
+
+
+def gbdt_partition(bins: torch.Tensor, rows: torch.Tensor, seg: torch.Tensor, feature: torch.Tensor,
+                   threshold: torch.Tensor, first_right: Optional[torch.Tensor] = None, out=None, stream=None):
+    """K17: ``(rows2, seg2)``, the stable two-way partition of every segment of a K16 table (the
+    definition: :func:`mp4x.parallel.gbdt.gbdt_partition_torch`).  ``rows2`` int32 ``[m]``, ``seg2`` int64
+    ``[2k + 1]``: segment j holds the first rows of node j, segment ``k + j`` its second rows, in slot
+    order.  Only ``rows2[:seg2[2k]]`` is written, every slot once; a fresh ``rows2`` is filled with -1
+    first, ``out=(rows2, seg2)`` is used as it is (``rows2`` may not overlap ``rows``).  The table and the
+    split records are read on the device only."""
+    _dev_check(bins, rows, seg, feature, threshold, first_right, *(out or ()))
+    if bins.dtype != torch.uint8 or bins.dim() != 2 or bins.shape[1] < 1:
+        raise ValueError("gbdt_partition: bins must be uint8 [n, F] with F >= 1")
+    if rows.dtype != torch.int32 or rows.dim() != 1 or seg.dtype != torch.int64 or seg.dim() != 1 or seg.numel() < 1:
+        raise ValueError("gbdt_partition: rows must be int32 [m] and seg int64 [k + 1]")
+    (n, F), m, k = bins.shape, rows.numel(), seg.numel() - 1
+    if n >= 2 ** 31 or m >= 2 ** 31 or k > GBDT_MAX_PARENTS:
+        raise ValueError(f"gbdt_partition: n and m must be below 2**31 and k at most {GBDT_MAX_PARENTS}")
+    for name, t in (("feature", feature), ("threshold", threshold), ("first_right", first_right)):
+        if t is not None and (t.dtype != torch.int32 or tuple(t.shape) != (k,) or not t.is_contiguous()):
+            raise ValueError(f"gbdt_partition: {name} must be a contiguous int32 [{k}]")
+    rows2 = torch.full((m,), -1, dtype=torch.int32, device=bins.device) if out is None else \
+        _gbdt_out("gbdt_partition", out[0], (m,), torch.int32, bins.device)
+    seg2 = _gbdt_out("gbdt_partition", None if out is None else out[1], (2 * k + 1,), torch.int64, bins.device)
+    lib = native.hip()
+    sb = lib.mp4x_gbdt_partition_scratch_bytes(m, k)
+    scratch = torch.empty(max(sb, 16) // 16 + 1, 2, dtype=torch.int64, device=bins.device)
+    live = bool(n and m and k)
+    check(lib.mp4x_gbdt_partition(bins.data_ptr() if live else None, rows.data_ptr() if live else None, seg.data_ptr(),
+                                  feature.data_ptr() if live else None, threshold.data_ptr() if live else None,
+                                  first_right.data_ptr() if live and first_right is not None else None, n, F, m, k,
+                                  rows2.data_ptr() if live else None, seg2.data_ptr(), scratch.data_ptr(), sb,
+                                  stream_ptr(stream)), "mp4x_gbdt_partition")
+    return rows2, seg2
+
+
+def gbdt_hist_subtract(parent: torch.Tensor, small: torch.Tensor, parent_of: torch.Tensor,
+                       out: Optional[torch.Tensor] = None, stream=None) -> torch.Tensor:
+    """K17: ``large[p] = parent[parent_of[p]] - small[p]`` in wrapping int64: the sibling of a child whose
+    histogram is ``small[p]`` under the parent ``parent_of[p]`` (outside ``[0, k)``: a zero histogram).
+    ``parent`` int64 ``[k, F, B, 2]``, ``small`` int64 ``[kp, F, B, 2]``, ``parent_of`` int32 ``[kp]``."""
+    _dev_check(parent, small, parent_of, out)
+    if parent.dtype != torch.int64 or parent.dim() != 4 or parent.shape[3] != 2 or small.dtype != torch.int64 or \
+            small.dim() != 4 or tuple(small.shape[1:]) != tuple(parent.shape[1:]) or parent.shape[1] * parent.shape[2] < 1:
+        raise ValueError("gbdt_hist_subtract: parent must be int64 [k, F, B, 2] and small int64 [kp, F, B, 2]")
+    k, kp, cells = parent.shape[0], small.shape[0], parent.shape[1] * parent.shape[2]
+    if parent_of.dtype != torch.int32 or tuple(parent_of.shape) != (kp,) or k > GBDT_MAX_NODES or kp > GBDT_MAX_NODES:
+        raise ValueError(f"gbdt_hist_subtract: parent_of must be int32 [{kp}] and k, kp at most {GBDT_MAX_NODES}")
+    out = _gbdt_out("gbdt_hist_subtract", out, tuple(small.shape), torch.int64, parent.device)
+    check(native.hip().mp4x_gbdt_hist_subtract(parent.data_ptr() if k else None, small.data_ptr() if kp else None,
+                                               parent_of.data_ptr() if kp else None, k, kp, cells,
+                                               out.data_ptr() if kp else None, stream_ptr(stream)),
+          "mp4x_gbdt_hist_subtract")
+    return out
+
+
 MOE_COMBINE_BWD_MAX_TOP_K = 16       # csrc/kernels/moe.hip: kMoeBwdMaxK
 
 

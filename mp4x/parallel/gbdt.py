@@ -66,11 +66,12 @@ def _clamped_bounds(seg: torch.Tensor, m: int) -> List[int]:
     return c
 
 
-def gbdt_hist_torch(bins: torch.Tensor, gh: torch.Tensor, rows: torch.Tensor, seg: torch.Tensor, B: int) -> torch.Tensor:
+def gbdt_hist_torch(bins: torch.Tensor, gh: torch.Tensor, rows: torch.Tensor, seg: torch.Tensor, B: int,
+                    out: torch.Tensor = None) -> torch.Tensor:
     """``hist`` int64 ``[k, F, B, 2]``: ``hist[j, f, b] = sum gh[r]`` over ``r in rows[c[j]:c[j+1]]`` with
     ``bins[r, f] == b``; ``c[0] = 0``, ``c[j+1] = max(c[j], min(seg[j+1], m))`` (any table is legal), a
     row index outside ``[0, n)`` and a bin value ``>= B`` (a missing value) are skipped.  The CPU form
-    reads the table on the host; the kernel does not."""
+    reads the table on the host; the kernel does not.  ``out`` receives the result."""
     if isinstance(B, bool) or not isinstance(B, int) or not 2 <= B <= 256:
         raise ValueError(f"B {B!r} must be an int in [2, 256]")
     if bins.dtype != torch.uint8 or bins.dim() != 2 or gh.dtype != torch.int32 or tuple(gh.shape) != (bins.shape[0], 2):
@@ -79,7 +80,8 @@ def gbdt_hist_torch(bins: torch.Tensor, gh: torch.Tensor, rows: torch.Tensor, se
         raise ValueError("rows must be int32 [m] and seg int64 [k + 1]")
     if bins.is_cuda:
         from ..ops import device_ops
-        return device_ops.gbdt_histogram(bins.contiguous(), gh.contiguous(), rows.contiguous(), seg.contiguous(), B)
+        return device_ops.gbdt_histogram(bins.contiguous(), gh.contiguous(), rows.contiguous(), seg.contiguous(), B,
+                                         out=out)
     n, F = bins.shape
     m, k = rows.numel(), seg.numel() - 1
     c = _clamped_bounds(seg, m)
@@ -93,6 +95,8 @@ def gbdt_hist_torch(bins: torch.Tensor, gh: torch.Tensor, rows: torch.Tensor, se
     val = gh[r].to(torch.int64)[:, None, :].expand(-1, F, -1)
     hist = torch.zeros(k * F * B, 2, dtype=torch.int64)
     hist.index_add_(0, cell[live], val[live])
+    if out is not None:
+        return out.copy_(hist.view(k, F, B, 2))
     return hist.view(k, F, B, 2)
 
 
@@ -137,6 +141,76 @@ def gbdt_split_torch(hist: torch.Tensor, sg: int, sh: int, lam: float) -> GbdtSp
                      Gi[rows, f, 0], Hi[rows, f, 0])
 
 
+# ---------------------------------------------------------------- the level advance (K17)
+def gbdt_partition_torch(bins: torch.Tensor, rows: torch.Tensor, seg: torch.Tensor, feature: torch.Tensor,
+                         threshold: torch.Tensor, first_right: torch.Tensor = None, out=None):
+    """``(rows2, seg2)``: the stable two-way partition of every segment of a level.  ``seg`` int64 ``[k +
+    1]`` is :func:`gbdt_hist_torch`'s table over ``rows`` int32 ``[m]`` (clamped the same way, any table is
+    legal), ``feature``, ``threshold``, ``first_right`` int32 ``[k]`` (``first_right`` defaults to 0), ``k <=
+    2048``.  Node j splits iff ``0 <= feature[j] < F``; the rows of a node that does not split and a slot
+    whose row index is outside ``[0, n)`` are dropped.  Row r of a splitting node goes right iff
+    ``int(bins[r, feature[j]]) > threshold[j]`` (any int32 threshold; the trainer's rule, a missing-value
+    bin goes right) and is "first" iff ``went_right == (first_right[j] != 0)``, else "second".  ``seg2``
+    int64 ``[2k + 1]`` from 0: segment j of ``rows2`` holds node j's first rows, segment ``k + j`` its second
+    rows, in slot order, so ``seg2[:k + 1]`` is the table of the first children alone.  Only
+    ``rows2[:seg2[2k]]`` is defined: the CPU form fills the rest with -1, the kernels leave it alone.
+    ``out=(rows2, seg2)`` receives the result."""
+    if bins.dtype != torch.uint8 or bins.dim() != 2 or bins.shape[1] < 1:
+        raise ValueError("bins must be uint8 [n, F] with F >= 1")
+    if rows.dtype != torch.int32 or rows.dim() != 1 or seg.dtype != torch.int64 or seg.dim() != 1 or seg.numel() < 1:
+        raise ValueError("rows must be int32 [m] and seg int64 [k + 1]")
+    (n, F), m, k = bins.shape, rows.numel(), seg.numel() - 1
+    if first_right is None:
+        first_right = torch.zeros(k, dtype=torch.int32, device=bins.device)
+    if k > 2048 or any(t.dtype != torch.int32 or tuple(t.shape) != (k,) for t in (feature, threshold, first_right)):
+        raise ValueError("feature, threshold and first_right must be int32 [k] with k <= 2048")
+    if bins.is_cuda:
+        from ..ops import device_ops
+        return device_ops.gbdt_partition(bins.contiguous(), rows.contiguous(), seg.contiguous(), feature.contiguous(),
+                                         threshold.contiguous(), first_right.contiguous(), out=out)
+    c = _clamped_bounds(seg, m)
+    node = torch.repeat_interleave(torch.arange(k), torch.tensor([c[j + 1] - c[j] for j in range(k)], dtype=torch.int64))
+    r = rows[:c[k]].to(torch.int64)
+    f = feature.to(torch.int64)[node]
+    live = (r >= 0) & (r < n) & (f >= 0) & (f < F)
+    r, f, node = r[live], f[live], node[live]
+    right = bins[r, f].to(torch.int64) > threshold.to(torch.int64)[node]
+    key = torch.where(right == (first_right[node] != 0), node, node + k)
+    rows2 = torch.full((m,), -1, dtype=torch.int32)
+    rows2[:r.numel()] = r[torch.sort(key, stable=True).indices].to(torch.int32)
+    seg2 = torch.zeros(2 * k + 1, dtype=torch.int64)
+    seg2[1:] = torch.cumsum(torch.bincount(key, minlength=2 * k), 0)
+    if out is not None:
+        out[0].copy_(rows2)
+        out[1].copy_(seg2)
+        return out[0], out[1]
+    return rows2, seg2
+
+
+def gbdt_hist_subtract_torch(parent: torch.Tensor, small: torch.Tensor, parent_of: torch.Tensor,
+                             out: torch.Tensor = None) -> torch.Tensor:
+    """Sibling subtraction: ``large[p] = parent[parent_of[p]] - small[p]`` in wrapping int64, ``parent``
+    int64 ``[k, F, B, 2]``, ``small`` int64 ``[kp, F, B, 2]``, ``parent_of`` int32 ``[kp]``; a ``parent_of[p]``
+    outside ``[0, k)`` reads a zero histogram.  Histograms are exact integer sums, so this is the other
+    child's histogram bit for bit."""
+    if parent.dtype != torch.int64 or parent.dim() != 4 or parent.shape[3] != 2 or small.dtype != torch.int64 or \
+            small.dim() != 4 or small.shape[1:] != parent.shape[1:] or parent_of.dtype != torch.int32 or \
+            tuple(parent_of.shape) != (small.shape[0],):
+        raise ValueError("parent must be int64 [k, F, B, 2], small int64 [kp, F, B, 2] and parent_of int32 [kp]")
+    if parent.is_cuda:
+        from ..ops import device_ops
+        return device_ops.gbdt_hist_subtract(parent.contiguous(), small.contiguous(), parent_of.contiguous(), out=out)
+    k = parent.shape[0]
+    j = parent_of.to(torch.int64)
+    inside = (j >= 0) & (j < k)
+    zero = torch.zeros((1,) + tuple(parent.shape[1:]), dtype=torch.int64)
+    large = torch.cat([parent, zero])[torch.where(inside, j, torch.full_like(j, k))] - small
+    if out is not None:
+        out.copy_(large)
+        return out
+    return large
+
+
 # ---------------------------------------------------------------- the trainer
 def _allreduce(comm, t: torch.Tensor, operand, operator) -> torch.Tensor:
     """In-place allreduce of a flat tensor over the job: the device engine for a GPU tensor, the host
@@ -166,14 +240,28 @@ def gbdt_level_rows(node_of: torch.Tensor, slot_of_node: torch.Tensor, k: int):
 
 
 def train_gbdt_quantized(comm, bins: torch.Tensor, y: torch.Tensor, B: int, trees: int = 5, depth: int = 3,
-                         lr: float = 0.3, lam: float = 1.0) -> List[Tree]:
+                         lr: float = 0.3, lam: float = 1.0, level: str = "sort", subtract: bool = False) -> List[Tree]:
     """:func:`mp4x.models.gbdt.train_gbdt` on fixed-point statistics: ``bins`` uint8 ``[n, F]`` and ``y``
     ``[n]`` are this rank's rows, torch tensors on the CPU or the GPU.  Squared loss: ``g = float32(pred -
     y)``, ``h = 1``.  Per tree one allreduce MAX of ``(max|g|, max|h|)`` fixes the shifts and the rows are
     quantised once; per level the rows are grouped by node, one histogram call and one int64 SUM allreduce
     give the job's histograms, one split call the ``k`` records the tree grows from on the host, and
     ``node_of`` moves elementwise.  Every step is per row or in integers: the trees are bit for bit the
-    same for every rank count and on either device."""
+    same for every rank count and on either device.
+
+    ``level`` is how a level's rows are grouped: ``"sort"`` sorts all rows by node
+    (:func:`gbdt_level_rows`); ``"partition"`` keeps the rows grouped from level to level and splits every
+    segment in two with :func:`gbdt_partition_torch` (K17), two row buffers in turn, the split records
+    uploaded per segment and the next table taken from ``seg2`` by device indexing.  ``subtract=True``
+    (``level="partition"`` only) puts the child with the smaller hessian mass first (right iff ``H - HL <
+    HL`` of the allreduced record: the same on every rank), histograms and allreduces the first children
+    alone and takes every sibling as parent - child (:func:`gbdt_hist_subtract_torch`), exactly.  Both
+    grow the default's trees bit for bit."""
+    if level not in ("sort", "partition"):
+        raise ValueError(f"level {level!r} must be 'sort' or 'partition'")
+    if subtract and level != "partition":
+        raise ValueError("subtract=True needs level='partition'")
+    part = level == "partition"
     dev = bins.device
     n, F = bins.shape
     y = y.to(device=dev, dtype=torch.float64)
@@ -190,24 +278,41 @@ def train_gbdt_quantized(comm, bins: torch.Tensor, y: torch.Tensor, B: int, tree
         node_of = torch.zeros(n, dtype=torch.int64, device=dev)
         tree = Tree([-1], [-1], [-1], [-1], [0.0])
         frontier = [0]
-        for level in range(depth + 1):
+        seg_nodes = [0]                                   # partition: the tree node of every segment
+        if part:
+            rows, spare = torch.arange(n, dtype=torch.int32, device=dev), torch.empty(n, dtype=torch.int32, device=dev)
+            seg = torch.tensor([0, n], dtype=torch.int64, device=dev)
+        hist, parents = None, []
+        for level_no in range(depth + 1):
             k = len(frontier)
-            slot_of_node = torch.full((len(tree.value),), -1, dtype=torch.int64)
-            slot_of_node[frontier] = torch.arange(k)
-            rows, seg = gbdt_level_rows(node_of, slot_of_node.to(dev), k)
-            hist = gbdt_hist_torch(bins, gh, rows, seg, B)
-            _allreduce(comm, hist.view(-1), Operands.LONG_OPERAND(), Operators.Long.SUM)
+            if not part:
+                slot_of_node = torch.full((len(tree.value),), -1, dtype=torch.int64)
+                slot_of_node[frontier] = torch.arange(k)
+                rows, seg = gbdt_level_rows(node_of, slot_of_node.to(dev), k)
+            if subtract and parents:
+                kp = len(parents)
+                both = torch.empty((2 * kp,) + tuple(hist.shape[1:]), dtype=torch.int64, device=dev)
+                gbdt_hist_torch(bins, gh, rows, seg[:kp + 1], B, out=both[:kp])
+                _allreduce(comm, both[:kp].view(-1), Operands.LONG_OPERAND(), Operators.Long.SUM)
+                gbdt_hist_subtract_torch(hist, both[:kp], torch.tensor(parents, dtype=torch.int32, device=dev),
+                                         out=both[kp:])
+                hist = both
+            else:
+                hist = gbdt_hist_torch(bins, gh, rows, seg, B)
+                _allreduce(comm, hist.view(-1), Operands.LONG_OPERAND(), Operators.Long.SUM)
             best = gbdt_split_torch(hist, sg, sh, lam)
             rec = [t.tolist() for t in best]
             feat_of = torch.full((len(tree.value),), -1, dtype=torch.int64)
             thr_of = torch.zeros(len(tree.value), dtype=torch.int64)
             left_of = torch.zeros(len(tree.value), dtype=torch.int64)
+            seg_of = {nd: i for i, nd in enumerate(seg_nodes)} if part else {nd: i for i, nd in enumerate(frontier)}
             new_frontier = []
-            for i, nd in enumerate(frontier):
+            for nd in frontier:
+                i = seg_of[nd]
                 f, t = rec[1][i], rec[2][i]
                 G, H = math.ldexp(rec[5][i], -sg), math.ldexp(rec[6][i], -sh)
                 tree.value[nd] = -G / (H + lam) * lr
-                if level == depth or H < 2 or f < 0:
+                if level_no == depth or H < 2 or f < 0:
                     continue
                 li = len(tree.value)
                 for _ in range(2):
@@ -221,6 +326,18 @@ def train_gbdt_quantized(comm, bins: torch.Tensor, y: torch.Tensor, B: int, tree
                 new_frontier += [li, li + 1]
             if not new_frontier:
                 break
+            if part:
+                # per segment: the split (-1: a final leaf) and which child stands first
+                sf = [tree.feature[nd] for nd in seg_nodes]
+                fr = [int(subtract and f >= 0 and rec[6][i] - rec[4][i] < rec[4][i]) for i, f in enumerate(sf)]
+                up = torch.tensor([sf, [tree.threshold[nd] for nd in seg_nodes], fr], dtype=torch.int32).to(dev)
+                seg2 = torch.empty(2 * k + 1, dtype=torch.int64, device=dev)
+                gbdt_partition_torch(bins, rows, seg, up[0], up[1], up[2], out=(spare, seg2))
+                rows, spare = spare, rows
+                parents = [i for i, f in enumerate(sf) if f >= 0]
+                seg = seg2[torch.tensor(parents + [k + i for i in parents] + [2 * k]).to(dev)]
+                seg_nodes = [tree.left[seg_nodes[i]] + fr[i] for i in parents] + \
+                            [tree.left[seg_nodes[i]] + 1 - fr[i] for i in parents]
             feat_of, thr_of, left_of = feat_of.to(dev), thr_of.to(dev), left_of.to(dev)
             f_row = feat_of[node_of]
             moves = f_row >= 0
