@@ -277,7 +277,8 @@ using namespace mp4x;
 
 extern "C" int mp4x_gbdt_quantize(const float* g, const float* h, int64_t n, int shift_g, int shift_h, int32_t* gh,
                                   void* stream) {
-  if (n < 0 || n >= gm::kMaxRows || shift_g < -200 || shift_g > 200 || shift_h < -200 || shift_h > 200)
+  if (n < 0 || n >= gm::kMaxRows || shift_g < -gm::kMaxShift || shift_g > gm::kMaxShift || shift_h < -gm::kMaxShift ||
+      shift_h > gm::kMaxShift)
     return MP4X_E_BADARG;
   if (n == 0) return 0;
   if (!g || ((uintptr_t)g & 7) || !h || ((uintptr_t)h & 7) || !gh || ((uintptr_t)gh & 15)) return MP4X_E_BADARG;
@@ -330,8 +331,8 @@ extern "C" int mp4x_gbdt_split(const int64_t* hist, int64_t k, int64_t F, int B,
                                double* gain, int32_t* feature, int32_t* threshold, int64_t* GL, int64_t* HL, int64_t* G,
                                int64_t* H, void* scratch, size_t scratch_bytes, void* stream) {
   hipStream_t st = (hipStream_t)stream;
-  if (k < 0 || F < 1 || B < 2 || B > gm::kMaxBins || k * F >= gm::kMaxRows || shift_g < -200 || shift_g > 200 ||
-      shift_h < -200 || shift_h > 200)
+  if (k < 0 || F < 1 || B < 2 || B > gm::kMaxBins || k * F >= gm::kMaxRows || shift_g < -gm::kMaxShift ||
+      shift_g > gm::kMaxShift || shift_h < -gm::kMaxShift || shift_h > gm::kMaxShift)
     return MP4X_E_BADARG;
   if (k == 0) return 0;
   if (!hist || ((uintptr_t)hist & 7) || !gain || ((uintptr_t)gain & 7) || !feature || ((uintptr_t)feature & 3) ||

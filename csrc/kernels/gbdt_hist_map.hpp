@@ -45,6 +45,7 @@ constexpr int kWaves = 4;                        // waves a block (kBlock / 64)
 constexpr int kTile = 4096;                      // row slots a tile
 constexpr int kMaxNodes = 4096;                  // k: the table fits one block's LDS
 constexpr int kMaxBins = 256;                    // bins are bytes
+constexpr int kMaxShift = 200;                   // |s|: float64(x) * 2**s stays exact for every float32 x
 constexpr int kLdsBytes = 32768;                 // private histogram a block: fg * B * 16 bytes
 constexpr int64_t kMaxRows = (int64_t)1 << 31;   // m, n < this: slots and rows are 32-bit
 

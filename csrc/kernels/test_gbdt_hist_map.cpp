@@ -1,13 +1,15 @@
 // Stand-alone CPU test of the tile map of the GBDT histogram (gbdt_hist_map.hpp): for every table
 // below and a few (F, B) it builds c and T as the kernel does and walks every block id and every
 // thread of the grid a launch would build, and checks invariants H1 .. H3 of the header.  Built by
-// tests/test_gbdt_hist_map_cpu.py with -fsanitize=address,undefined (the tables live in exactly
+// tests/test_kernel_maps_cpu.py with -fsanitize=address,undefined (the tables live in exactly
 // sized heap arrays, so a read past one is an error).  Prints OK.
 #include <cstdio>
 #include <cstdlib>
 #include <vector>
 
 #include "gbdt_hist_map.hpp"
+#define MAP_TEST_SUBJECT c.name
+#include "test_map_common.hpp"
 
 namespace gm = mp4x::gbdt_map;
 
@@ -16,17 +18,6 @@ struct Case {
   std::vector<int64_t> seg;      // k + 1 entries
   int64_t m;
 };
-
-static int failures = 0;
-#define CHECK(cond, ...)                                  \
-  do {                                                    \
-    if (!(cond)) {                                        \
-      std::printf("FAIL %s: ", c.name);                   \
-      std::printf(__VA_ARGS__);                           \
-      std::printf(" (%s, line %d)\n", #cond, __LINE__);   \
-      if (++failures > 20) std::exit(1);                  \
-    }                                                     \
-  } while (0)
 
 static Case lengths(const char* name, std::vector<int64_t> len, int64_t tail) {
   Case c{name, {0}, 0};
@@ -130,10 +121,5 @@ int main() {
   for (const Case& c : cases)
     for (int64_t F : Fs)
       for (int B : Bs) run(c, F, B);
-  if (failures) {
-    std::printf("%d failure(s)\n", failures);
-    return 1;
-  }
-  std::printf("OK %zu tables\n", cases.size());
-  return 0;
+  return map_test::report("OK %zu tables\n", cases.size());
 }

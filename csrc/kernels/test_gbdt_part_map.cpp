@@ -1,7 +1,7 @@
 // Stand-alone CPU test of the destination map of the GBDT row partition (gbdt_part_map.hpp): for
 // every table below it runs the count, offsets and scatter steps of gbdt_level.hip as plain loops over
 // every tile, wave, step and lane, through the header's functions and the header's scratch layout,
-// and checks invariants P1 .. P3 of the header.  Built by tests/test_gbdt_part_map_cpu.py with
+// and checks invariants P1 .. P3 of the header.  Built by tests/test_kernel_maps_cpu.py with
 // -fsanitize=address,undefined (the scratch and the outputs are exactly sized heap arrays, so an
 // access past one is an error).  Prints OK.
 #include <cstdio>
@@ -10,6 +10,8 @@
 #include <vector>
 
 #include "gbdt_part_map.hpp"
+#define MAP_TEST_SUBJECT c.name
+#include "test_map_common.hpp"
 
 namespace gm = mp4x::gbdt_map;
 namespace gp = mp4x::gbdt_part;
@@ -19,17 +21,6 @@ struct Case {
   std::vector<int64_t> seg;      // k + 1 entries
   int64_t m;
 };
-
-static int failures = 0;
-#define CHECK(cond, ...)                                  \
-  do {                                                    \
-    if (!(cond)) {                                        \
-      std::printf("FAIL %s: ", c.name);                   \
-      std::printf(__VA_ARGS__);                           \
-      std::printf(" (%s, line %d)\n", #cond, __LINE__);   \
-      if (++failures > 20) std::exit(1);                  \
-    }                                                     \
-  } while (0)
 
 static Case lengths(const char* name, std::vector<int64_t> len, int64_t tail) {
   Case c{name, {0}, 0};
@@ -202,10 +193,5 @@ int main() {
   const int64_t Fs[] = {1, 37};
   for (const Case& c : cases)
     for (int64_t F : Fs) run(c, F);
-  if (failures) {
-    std::printf("%d failure(s)\n", failures);
-    return 1;
-  }
-  std::printf("OK %zu tables\n", cases.size());
-  return 0;
+  return map_test::report("OK %zu tables\n", cases.size());
 }

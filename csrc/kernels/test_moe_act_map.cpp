@@ -1,6 +1,6 @@
 // Stand-alone CPU test of the row rule of the gated expert activation (moe_act_map.hpp): for every
 // table below, every item count and a few grids it walks every wave and lane as a kernel would and
-// checks invariants J1 .. J4 of the header.  Built by tests/test_moe_act_map_cpu.py with
+// checks invariants J1 .. J4 of the header.  Built by tests/test_kernel_maps_cpu.py with
 // -fsanitize=address,undefined (the tables live in exactly sized heap arrays, so a read past one is
 // an error).  Prints OK.
 #include <cstdio>
@@ -8,6 +8,8 @@
 #include <vector>
 
 #include "moe_act_map.hpp"
+#define MAP_TEST_SUBJECT c.name
+#include "test_map_common.hpp"
 
 namespace am = mp4x::act_map;
 
@@ -17,17 +19,6 @@ struct Case {
   std::vector<int64_t> table;      // ragged: offsets [G + 1]; padded: valid [G * B]
   int64_t R, G, B, S;
 };
-
-static int failures = 0;
-#define CHECK(cond, ...)                                  \
-  do {                                                    \
-    if (!(cond)) {                                        \
-      std::printf("FAIL %s: ", c.name);                   \
-      std::printf(__VA_ARGS__);                           \
-      std::printf(" (%s, line %d)\n", #cond, __LINE__);   \
-      if (++failures > 20) std::exit(1);                  \
-    }                                                     \
-  } while (0)
 
 static Case ragged(const char* name, std::vector<int64_t> lengths, int64_t tail) {
   Case c{name, am::kRagged, {0}, 0, (int64_t)lengths.size(), 1, 1};
@@ -181,10 +172,5 @@ int main() {
   for (const Case& c : cases)
     for (int64_t n : items)
       for (int64_t w : grids) run(c, n, w);
-  if (failures) {
-    std::printf("%d failure(s)\n", failures);
-    return 1;
-  }
-  std::printf("OK %zu tables\n", cases.size());
-  return 0;
+  return map_test::report("OK %zu tables\n", cases.size());
 }

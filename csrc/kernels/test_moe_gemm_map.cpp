@@ -1,12 +1,14 @@
 // Stand-alone CPU test of the tile map of the grouped expert GEMM (moe_gemm_map.hpp): for every table
 // below and every block id of the grids a launcher would build it walks the map and checks invariants
-// I1 .. I4 of the header.  Built by tests/test_moe_gemm_map_cpu.py with -fsanitize=address,undefined
+// I1 .. I4 of the header.  Built by tests/test_kernel_maps_cpu.py with -fsanitize=address,undefined
 // (the tables live in exactly sized heap arrays, so a read past one is an error).  Prints OK.
 #include <cstdio>
 #include <cstdlib>
 #include <vector>
 
 #include "moe_gemm_map.hpp"
+#define MAP_TEST_SUBJECT c.name
+#include "test_map_common.hpp"
 
 namespace gm = mp4x::gemm_map;
 
@@ -21,17 +23,6 @@ struct Case {
   int64_t R, G, B, S;
   std::vector<Seg> want;           // the clamped segments, written out from the rule (empty ones left out)
 };
-
-static int failures = 0;
-#define CHECK(cond, ...)                                  \
-  do {                                                    \
-    if (!(cond)) {                                        \
-      std::printf("FAIL %s: ", c.name);                   \
-      std::printf(__VA_ARGS__);                           \
-      std::printf(" (%s, line %d)\n", #cond, __LINE__);   \
-      if (++failures > 20) std::exit(1);                  \
-    }                                                     \
-  } while (0)
 
 static Case ragged(const char* name, std::vector<int64_t> lengths, int64_t tail) {
   Case c{name, gm::kRagged, {0}, 0, (int64_t)lengths.size(), 1, 1, {}};
@@ -137,10 +128,5 @@ int main() {
   for (const Case& c : cases)
     for (int64_t BM : BMs)
       for (int64_t BK : BKs) run(c, BM, BK);
-  if (failures) {
-    std::printf("%d failure(s)\n", failures);
-    return 1;
-  }
-  std::printf("OK %zu tables\n", cases.size());
-  return 0;
+  return map_test::report("OK %zu tables\n", cases.size());
 }

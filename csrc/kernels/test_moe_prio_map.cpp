@@ -12,16 +12,9 @@
 #include <vector>
 
 #include "moe_prio_map.hpp"
+#include "test_map_common.hpp"
 
 using namespace mp4x;
-
-static int failures = 0;
-#define CHECK(cond)                                                     \
-  do {                                                                  \
-    if (!(cond)) {                                                      \
-      if (++failures < 20) std::printf("FAIL %s:%d %s\n", __FILE__, __LINE__, #cond); \
-    }                                                                   \
-  } while (0)
 
 static uint32_t bits_of(float f) {
   uint32_t u;
@@ -170,10 +163,5 @@ int main() {
     }
     check_segment(p, idx, false);
   }
-  if (failures) {
-    std::printf("FAILED %d checks\n", failures);
-    return 1;
-  }
-  std::printf("OK\n");
-  return 0;
+  return map_test::report("OK\n");
 }

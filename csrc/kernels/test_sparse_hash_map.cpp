@@ -12,16 +12,9 @@
 #include <vector>
 
 #include "sparse_hash_map.hpp"
+#include "test_map_common.hpp"
 
 using namespace mp4x;
-
-static int failures = 0;
-#define CHECK(cond)                                                     \
-  do {                                                                  \
-    if (!(cond)) {                                                      \
-      if (++failures < 20) std::printf("FAIL %s:%d %s\n", __FILE__, __LINE__, #cond); \
-    }                                                                   \
-  } while (0)
 
 static uint64_t rng_state = 0x9e3779b97f4a7c15ull;
 static uint64_t rnd() {
@@ -203,10 +196,5 @@ int main() {
     run_case(one, 8);
   }
   CHECK(max_adv < 1024 / 2 + 1);                         // far from the advance bound t
-  if (failures) {
-    std::printf("FAILED %d checks\n", failures);
-    return 1;
-  }
-  std::printf("OK max advances %llu, max steps %llu\n", (unsigned long long)max_adv, (unsigned long long)max_it);
-  return 0;
+  return map_test::report("OK max advances %llu, max steps %llu\n", (unsigned long long)max_adv, (unsigned long long)max_it);
 }

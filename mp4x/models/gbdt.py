@@ -26,6 +26,15 @@ class Tree:
     right: List[int] = field(default_factory=list)
     value: List[float] = field(default_factory=list)
 
+    def split(self, node: int, feature: int, threshold: int) -> int:
+        """Make ``node`` an inner node with two new leaves; the left child's index (the right one follows)."""
+        left = len(self.value)
+        for column in (self.feature, self.threshold, self.left, self.right):
+            column += [-1, -1]
+        self.value += [0.0, 0.0]
+        self.feature[node], self.threshold[node], self.left[node], self.right[node] = feature, threshold, left, left + 1
+        return left
+
     def predict_bins(self, B: np.ndarray) -> np.ndarray:
         out = np.empty(B.shape[0])
         for i in range(B.shape[0]):
@@ -85,14 +94,8 @@ def train_gbdt(comm, B: np.ndarray, y: np.ndarray, bins: int, trees: int = 5, de
                 f, t = np.unravel_index(int(np.argmax(gain)), gain.shape)
                 if gain[f, t] <= 1e-12:
                     continue
-                li, ri = len(tree.value), len(tree.value) + 1
-                for _ in range(2):
-                    tree.feature.append(-1)
-                    tree.threshold.append(-1)
-                    tree.left.append(-1)
-                    tree.right.append(-1)
-                    tree.value.append(0.0)
-                tree.feature[nd], tree.threshold[nd], tree.left[nd], tree.right[nd] = int(f), int(t), li, ri
+                li = tree.split(nd, int(f), int(t))
+                ri = li + 1
                 m = node_of == nd
                 go_left = B[:, f] <= t
                 node_of[m & go_left] = li

@@ -12,7 +12,7 @@ from typing import NamedTuple, Optional, Sequence, Tuple
 import torch
 
 from ..operators import DType, dtype_of_torch
-from . import native
+from . import gbdt_args, native
 from .native import check, ptr_array, stream_ptr
 
 QBLOCK = 256
@@ -683,16 +683,6 @@ def moe_priority_mask(rc: RouteCount, priority: torch.Tensor, limit, out: Option
     return out, masked
 
 
-GBDT_MAX_NODES = 4096                # csrc/kernels/gbdt_hist_map.hpp: kMaxNodes
-GBDT_MAX_SHIFT = 200
-
-
-def _gbdt_shift(fn: str, *shifts) -> None:
-    for s in shifts:
-        if isinstance(s, bool) or not isinstance(s, int) or abs(s) > GBDT_MAX_SHIFT:
-            raise ValueError(f"{fn}: the shift {s!r} is not an int in [-{GBDT_MAX_SHIFT}, {GBDT_MAX_SHIFT}]")
-
-
 def _gbdt_out(fn: str, out: Optional[torch.Tensor], shape, dtype, device) -> torch.Tensor:
     if out is None:
         return torch.empty(shape, dtype=dtype, device=device)
@@ -701,16 +691,15 @@ def _gbdt_out(fn: str, out: Optional[torch.Tensor], shape, dtype, device) -> tor
     return out
 
 
+# The argument rules both forms share are gbdt_args'; below them only the device's own: GPU tensors, sizes
+# below 2**31, alignment, the node caps and out=.
 def gbdt_quantize(g: torch.Tensor, h: torch.Tensor, sg: int, sh: int, out: Optional[torch.Tensor] = None,
                   stream=None) -> torch.Tensor:
     """K16: ``gh`` int32 ``[n, 2]`` with ``gh[r] = (q(g[r], sg), q(h[r], sh))``, ``q(x, s) =
     rint(float64(x) * 2**s)`` (half to even), NaN -> 0, clamped to ``+-(2**31 - 1)``; ``g``, ``h``
     float32 ``[n]``."""
     _dev_check(g, h, out)
-    _gbdt_shift("gbdt_quantize", sg, sh)
-    n = g.numel()
-    if g.dtype != torch.float32 or h.dtype != torch.float32 or g.dim() != 1 or tuple(h.shape) != (n,):
-        raise ValueError("gbdt_quantize: g and h must be float32 [n]")
+    n = gbdt_args.quantize(g, h, sg, sh)
     if n >= 2 ** 31 or g.data_ptr() & 7 or h.data_ptr() & 7:
         raise ValueError("gbdt_quantize: n must be below 2**31 and g, h 8-byte aligned")
     out = _gbdt_out("gbdt_quantize", out, (n, 2), torch.int32, g.device)
@@ -730,18 +719,11 @@ def gbdt_histogram(bins: torch.Tensor, gh: torch.Tensor, rows: torch.Tensor, seg
     device only, any content is legal.  A bin value ``>= B`` is skipped.  Integer atomics only: the same
     bits run to run.  ``out`` is zeroed by the call."""
     _dev_check(bins, gh, rows, seg, out)
-    if isinstance(B, bool) or not isinstance(B, int) or not 2 <= B <= 256:
-        raise ValueError(f"gbdt_histogram: B {B!r} must be an int in [2, 256]")
-    if bins.dtype != torch.uint8 or bins.dim() != 2 or bins.shape[1] < 1:
+    n, F, m, k = gbdt_args.histogram(bins, gh, rows, seg, B)
+    if F < 1:                                    # the kernel's grid is per feature group: none, no launch to make
         raise ValueError("gbdt_histogram: bins must be uint8 [n, F] with F >= 1")
-    n, F = bins.shape
-    if gh.dtype != torch.int32 or tuple(gh.shape) != (n, 2):
-        raise ValueError(f"gbdt_histogram: gh must be int32 [{n}, 2]")
-    if rows.dtype != torch.int32 or rows.dim() != 1 or seg.dtype != torch.int64 or seg.dim() != 1 or seg.numel() < 1:
-        raise ValueError("gbdt_histogram: rows must be int32 [m] and seg int64 [k + 1]")
-    m, k = rows.numel(), seg.numel() - 1
-    if n >= 2 ** 31 or m >= 2 ** 31 or k > GBDT_MAX_NODES or k * F * B >= 2 ** 31:
-        raise ValueError(f"gbdt_histogram: n, m and k * F * B must be below 2**31 and k at most {GBDT_MAX_NODES}")
+    if n >= 2 ** 31 or m >= 2 ** 31 or k > gbdt_args.MAX_NODES or k * F * B >= 2 ** 31:
+        raise ValueError(f"gbdt_histogram: n, m and k * F * B must be below 2**31 and k at most {gbdt_args.MAX_NODES}")
     out = _gbdt_out("gbdt_histogram", out, (k, F, B, 2), torch.int64, bins.device)
     lib = native.hip()
     sb = lib.mp4x_gbdt_hist_scratch_bytes(k)
@@ -769,13 +751,9 @@ def gbdt_best_split(hist: torch.Tensor, sg: int, sh: int, lam: float, out: Optio
     :func:`mp4x.parallel.gbdt.gbdt_split_torch`), float64 gains in the definition's order of
     operations, ties to the lower feature, then the lower threshold."""
     _dev_check(hist, *(out or ()))
-    _gbdt_shift("gbdt_best_split", sg, sh)
-    if hist.dtype != torch.int64 or hist.dim() != 4 or hist.shape[3] != 2 or hist.shape[1] < 1 or \
-            not 2 <= hist.shape[2] <= 256:
-        raise ValueError("gbdt_best_split: hist must be int64 [k, F, B, 2] with F >= 1 and 2 <= B <= 256")
-    k, F, B, _ = hist.shape
-    if k * F >= 2 ** 31:
-        raise ValueError("gbdt_best_split: k * F must be below 2**31")
+    k, F, B = gbdt_args.split(hist, sg, sh)
+    if B > gbdt_args.MAX_BINS or k * F >= 2 ** 31:          # the kernel keeps a node's bins in one wave's lanes
+        raise ValueError(f"gbdt_best_split: B must be at most {gbdt_args.MAX_BINS} and k * F below 2**31")
     dts = (torch.float64, torch.int32, torch.int32, torch.int64, torch.int64, torch.int64, torch.int64)
     o = GbdtSplit(*(_gbdt_out("gbdt_best_split", out[i] if out is not None else None, (k,), dt, hist.device)
                     for i, dt in enumerate(dts)))
@@ -788,9 +766,6 @@ def gbdt_best_split(hist: torch.Tensor, sg: int, sh: int, lam: float, out: Optio
     return o
 
 
-GBDT_MAX_PARENTS = GBDT_MAX_NODES // 2    # csrc/kernels/gbdt_part_map.hpp: kMaxParents
-
-
 def gbdt_partition(bins: torch.Tensor, rows: torch.Tensor, seg: torch.Tensor, feature: torch.Tensor,
                    threshold: torch.Tensor, first_right: Optional[torch.Tensor] = None, out=None, stream=None):
     """K17: ``(rows2, seg2)``, the stable two-way partition of every segment of a K16 table (the
@@ -800,16 +775,9 @@ def gbdt_partition(bins: torch.Tensor, rows: torch.Tensor, seg: torch.Tensor, fe
     first, ``out=(rows2, seg2)`` is used as it is (``rows2`` may not overlap ``rows``).  The table and the
     split records are read on the device only."""
     _dev_check(bins, rows, seg, feature, threshold, first_right, *(out or ()))
-    if bins.dtype != torch.uint8 or bins.dim() != 2 or bins.shape[1] < 1:
-        raise ValueError("gbdt_partition: bins must be uint8 [n, F] with F >= 1")
-    if rows.dtype != torch.int32 or rows.dim() != 1 or seg.dtype != torch.int64 or seg.dim() != 1 or seg.numel() < 1:
-        raise ValueError("gbdt_partition: rows must be int32 [m] and seg int64 [k + 1]")
-    (n, F), m, k = bins.shape, rows.numel(), seg.numel() - 1
-    if n >= 2 ** 31 or m >= 2 ** 31 or k > GBDT_MAX_PARENTS:
-        raise ValueError(f"gbdt_partition: n and m must be below 2**31 and k at most {GBDT_MAX_PARENTS}")
-    for name, t in (("feature", feature), ("threshold", threshold), ("first_right", first_right)):
-        if t is not None and (t.dtype != torch.int32 or tuple(t.shape) != (k,) or not t.is_contiguous()):
-            raise ValueError(f"gbdt_partition: {name} must be a contiguous int32 [{k}]")
+    n, F, m, k = gbdt_args.partition(bins, rows, seg, feature, threshold, first_right)
+    if n >= 2 ** 31 or m >= 2 ** 31:
+        raise ValueError("gbdt_partition: n and m must be below 2**31")
     rows2 = torch.full((m,), -1, dtype=torch.int32, device=bins.device) if out is None else \
         _gbdt_out("gbdt_partition", out[0], (m,), torch.int32, bins.device)
     seg2 = _gbdt_out("gbdt_partition", None if out is None else out[1], (2 * k + 1,), torch.int64, bins.device)
@@ -831,12 +799,9 @@ def gbdt_hist_subtract(parent: torch.Tensor, small: torch.Tensor, parent_of: tor
     histogram is ``small[p]`` under the parent ``parent_of[p]`` (outside ``[0, k)``: a zero histogram).
     ``parent`` int64 ``[k, F, B, 2]``, ``small`` int64 ``[kp, F, B, 2]``, ``parent_of`` int32 ``[kp]``."""
     _dev_check(parent, small, parent_of, out)
-    if parent.dtype != torch.int64 or parent.dim() != 4 or parent.shape[3] != 2 or small.dtype != torch.int64 or \
-            small.dim() != 4 or tuple(small.shape[1:]) != tuple(parent.shape[1:]) or parent.shape[1] * parent.shape[2] < 1:
-        raise ValueError("gbdt_hist_subtract: parent must be int64 [k, F, B, 2] and small int64 [kp, F, B, 2]")
-    k, kp, cells = parent.shape[0], small.shape[0], parent.shape[1] * parent.shape[2]
-    if parent_of.dtype != torch.int32 or tuple(parent_of.shape) != (kp,) or k > GBDT_MAX_NODES or kp > GBDT_MAX_NODES:
-        raise ValueError(f"gbdt_hist_subtract: parent_of must be int32 [{kp}] and k, kp at most {GBDT_MAX_NODES}")
+    k, kp, cells = gbdt_args.subtract(parent, small, parent_of)
+    if cells < 1 or k > gbdt_args.MAX_NODES or kp > gbdt_args.MAX_NODES:      # the native call's own argument rule
+        raise ValueError(f"gbdt_hist_subtract: F * B must be at least 1 and k, kp at most {gbdt_args.MAX_NODES}")
     out = _gbdt_out("gbdt_hist_subtract", out, tuple(small.shape), torch.int64, parent.device)
     check(native.hip().mp4x_gbdt_hist_subtract(parent.data_ptr() if k else None, small.data_ptr() if kp else None,
                                                parent_of.data_ptr() if kp else None, k, kp, cells,

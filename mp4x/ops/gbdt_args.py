@@ -1,0 +1,76 @@
+"""The argument rules of the fixed-point GBDT ops (K16, K17) and the limits behind them, stated once:
+the definitions of :mod:`mp4x.parallel.gbdt` and the wrappers of :mod:`mp4x.ops.device_ops` both call
+the op's function here, which checks what both forms require and returns the sizes.  What only the
+device requires (GPU tensors, sizes below ``2**31``, alignment, the node caps, ``out=``) stays with the
+wrapper.  Torch only: importing this loads no native library.  tests/test_native_abi_cpu.py compares the
+limits with csrc/kernels/gbdt_hist_map.hpp and gbdt_part_map.hpp."""
+from __future__ import annotations
+
+from typing import Optional, Tuple
+
+import torch
+
+MAX_SHIFT = 200                      # kMaxShift: float64(x) * 2**s is exact for every float32 x
+MAX_NODES = 4096                     # kMaxNodes: a histogram table fits one block's LDS
+MAX_PARENTS = MAX_NODES // 2         # kMaxParents: the 2k children stay a histogram table
+MAX_BINS = 256                       # kMaxBins: bins are bytes
+QMAX = 2 ** 31 - 1                   # a quantised gradient or hessian is clamped to +-QMAX
+
+
+def shifts(*s) -> None:
+    for x in s:
+        if isinstance(x, bool) or not isinstance(x, int) or abs(x) > MAX_SHIFT:
+            raise ValueError(f"the shift {x!r} is not an int in [-{MAX_SHIFT}, {MAX_SHIFT}]")
+
+
+def _table(rows: torch.Tensor, seg: torch.Tensor) -> Tuple[int, int]:
+    if rows.dtype != torch.int32 or rows.dim() != 1 or seg.dtype != torch.int64 or seg.dim() != 1 or seg.numel() < 1:
+        raise ValueError("rows must be int32 [m] and seg int64 [k + 1]")
+    return rows.numel(), seg.numel() - 1
+
+
+def quantize(g: torch.Tensor, h: torch.Tensor, sg: int, sh: int) -> int:
+    """``n``."""
+    shifts(sg, sh)
+    if g.dtype != torch.float32 or h.dtype != torch.float32 or g.dim() != 1 or h.shape != g.shape:
+        raise ValueError("g and h must be float32 [n]")
+    return g.numel()
+
+
+def histogram(bins: torch.Tensor, gh: torch.Tensor, rows: torch.Tensor, seg: torch.Tensor, B: int):
+    """``(n, F, m, k)``.  ``F = 0`` is the definition's to accept (an empty histogram) and the wrapper's to
+    refuse."""
+    if isinstance(B, bool) or not isinstance(B, int) or not 2 <= B <= MAX_BINS:
+        raise ValueError(f"B {B!r} must be an int in [2, {MAX_BINS}]")
+    if bins.dtype != torch.uint8 or bins.dim() != 2 or gh.dtype != torch.int32 or tuple(gh.shape) != (bins.shape[0], 2):
+        raise ValueError("bins must be uint8 [n, F] and gh int32 [n, 2]")
+    return tuple(bins.shape) + _table(rows, seg)
+
+
+def split(hist: torch.Tensor, sg: int, sh: int):
+    """``(k, F, B)``.  ``B <= MAX_BINS`` is the kernel's limit and stays with the wrapper."""
+    shifts(sg, sh)
+    if hist.dtype != torch.int64 or hist.dim() != 4 or hist.shape[3] != 2 or hist.shape[1] < 1 or hist.shape[2] < 2:
+        raise ValueError("hist must be int64 [k, F, B, 2] with F >= 1 and B >= 2")
+    return tuple(hist.shape[:3])
+
+
+def partition(bins: torch.Tensor, rows: torch.Tensor, seg: torch.Tensor, feature: torch.Tensor,
+              threshold: torch.Tensor, first_right: Optional[torch.Tensor]):
+    """``(n, F, m, k)``; ``first_right`` may be None (no node puts its right child first)."""
+    if bins.dtype != torch.uint8 or bins.dim() != 2 or bins.shape[1] < 1:
+        raise ValueError("bins must be uint8 [n, F] with F >= 1")
+    m, k = _table(rows, seg)
+    records = (feature, threshold) + (() if first_right is None else (first_right,))
+    if k > MAX_PARENTS or any(t.dtype != torch.int32 or tuple(t.shape) != (k,) for t in records):
+        raise ValueError(f"feature, threshold and first_right must be int32 [k] with k <= {MAX_PARENTS}")
+    return tuple(bins.shape) + (m, k)
+
+
+def subtract(parent: torch.Tensor, small: torch.Tensor, parent_of: torch.Tensor):
+    """``(k, kp, cells)`` with ``cells = F * B``."""
+    if parent.dtype != torch.int64 or parent.dim() != 4 or parent.shape[3] != 2 or small.dtype != torch.int64 or \
+            small.dim() != 4 or small.shape[1:] != parent.shape[1:] or parent_of.dtype != torch.int32 or \
+            tuple(parent_of.shape) != (small.shape[0],):
+        raise ValueError("parent must be int64 [k, F, B, 2], small int64 [kp, F, B, 2] and parent_of int32 [kp]")
+    return parent.shape[0], small.shape[0], parent.shape[1] * parent.shape[2]

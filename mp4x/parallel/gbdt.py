@@ -20,10 +20,10 @@ import torch
 from ..models.gbdt import Tree
 from ..operands import Operands
 from ..operators import Operators
+from ..ops import gbdt_args
 from ..ops.device_ops import GbdtSplit
+from ..ops.gbdt_args import MAX_SHIFT, QMAX
 
-QMAX = 2 ** 31 - 1
-MAX_SHIFT = 200
 MIN_GAIN = 1e-12
 
 
@@ -37,18 +37,10 @@ def gbdt_shift(maxabs: float) -> int:
     return max(-MAX_SHIFT, min(MAX_SHIFT, 30 - math.frexp(abs(maxabs))[1]))
 
 
-def _shifts(*shifts) -> None:
-    for s in shifts:
-        if isinstance(s, bool) or not isinstance(s, int) or abs(s) > MAX_SHIFT:
-            raise ValueError(f"the shift {s!r} is not an int in [-{MAX_SHIFT}, {MAX_SHIFT}]")
-
-
 def gbdt_quantize_torch(g: torch.Tensor, h: torch.Tensor, sg: int, sh: int) -> torch.Tensor:
     """``gh`` int32 ``[n, 2]``: ``q = rint(float64(x) * 2**s)``, half to even (the product only changes
     the exponent, so this is the one rounding), NaN -> 0, clamped to ``+-(2**31 - 1)``."""
-    _shifts(sg, sh)
-    if g.dtype != torch.float32 or h.dtype != torch.float32 or g.dim() != 1 or h.shape != g.shape:
-        raise ValueError("g and h must be float32 [n]")
+    gbdt_args.quantize(g, h, sg, sh)
     if g.is_cuda:
         from ..ops import device_ops
         return device_ops.gbdt_quantize(g.contiguous(), h.contiguous(), sg, sh)
@@ -72,18 +64,11 @@ def gbdt_hist_torch(bins: torch.Tensor, gh: torch.Tensor, rows: torch.Tensor, se
     ``bins[r, f] == b``; ``c[0] = 0``, ``c[j+1] = max(c[j], min(seg[j+1], m))`` (any table is legal), a
     row index outside ``[0, n)`` and a bin value ``>= B`` (a missing value) are skipped.  The CPU form
     reads the table on the host; the kernel does not.  ``out`` receives the result."""
-    if isinstance(B, bool) or not isinstance(B, int) or not 2 <= B <= 256:
-        raise ValueError(f"B {B!r} must be an int in [2, 256]")
-    if bins.dtype != torch.uint8 or bins.dim() != 2 or gh.dtype != torch.int32 or tuple(gh.shape) != (bins.shape[0], 2):
-        raise ValueError("bins must be uint8 [n, F] and gh int32 [n, 2]")
-    if rows.dtype != torch.int32 or rows.dim() != 1 or seg.dtype != torch.int64 or seg.dim() != 1 or seg.numel() < 1:
-        raise ValueError("rows must be int32 [m] and seg int64 [k + 1]")
+    n, F, m, k = gbdt_args.histogram(bins, gh, rows, seg, B)
     if bins.is_cuda:
         from ..ops import device_ops
         return device_ops.gbdt_histogram(bins.contiguous(), gh.contiguous(), rows.contiguous(), seg.contiguous(), B,
                                          out=out)
-    n, F = bins.shape
-    m, k = rows.numel(), seg.numel() - 1
     c = _clamped_bounds(seg, m)
     node = torch.repeat_interleave(torch.arange(k), torch.tensor([c[j + 1] - c[j] for j in range(k)], dtype=torch.int64))
     r = rows[:c[k]].to(torch.int64)
@@ -111,13 +96,10 @@ def gbdt_split_torch(hist: torch.Tensor, sg: int, sh: int, lam: float) -> GbdtSp
     lower f, then the lower t; a NaN or infinite gain never wins.  ``gain`` is the winner's (-inf
     without a finite gain); a node whose gain is ``<= 1e-12`` or not finite reports feature -1,
     threshold -1 and ``GL = HL = 0``.  ``G, H`` are the winning feature's, feature 0's without one."""
-    _shifts(sg, sh)
-    if hist.dtype != torch.int64 or hist.dim() != 4 or hist.shape[3] != 2 or hist.shape[1] < 1 or hist.shape[2] < 2:
-        raise ValueError("hist must be int64 [k, F, B, 2] with F >= 1 and B >= 2")
+    k, F, B = gbdt_args.split(hist, sg, sh)
     if hist.is_cuda:
         from ..ops import device_ops
         return device_ops.gbdt_best_split(hist.contiguous(), sg, sh, lam)
-    k, F, B, _ = hist.shape
     pre = torch.cumsum(hist, dim=2)
     GLi, HLi = pre[:, :, :-1, 0], pre[:, :, :-1, 1]                               # [k, F, B - 1]
     Gi, Hi = pre[:, :, -1:, 0], pre[:, :, -1:, 1]
@@ -147,7 +129,7 @@ def gbdt_partition_torch(bins: torch.Tensor, rows: torch.Tensor, seg: torch.Tens
     """``(rows2, seg2)``: the stable two-way partition of every segment of a level.  ``seg`` int64 ``[k +
     1]`` is :func:`gbdt_hist_torch`'s table over ``rows`` int32 ``[m]`` (clamped the same way, any table is
     legal), ``feature``, ``threshold``, ``first_right`` int32 ``[k]`` (``first_right`` defaults to 0), ``k <=
-    2048``.  Node j splits iff ``0 <= feature[j] < F``; the rows of a node that does not split and a slot
+    MAX_PARENTS`` (2048).  Node j splits iff ``0 <= feature[j] < F``; the rows of a node that does not split and a slot
     whose row index is outside ``[0, n)`` are dropped.  Row r of a splitting node goes right iff
     ``int(bins[r, feature[j]]) > threshold[j]`` (any int32 threshold; the trainer's rule, a missing-value
     bin goes right) and is "first" iff ``went_right == (first_right[j] != 0)``, else "second".  ``seg2``
@@ -155,15 +137,9 @@ def gbdt_partition_torch(bins: torch.Tensor, rows: torch.Tensor, seg: torch.Tens
     rows, in slot order, so ``seg2[:k + 1]`` is the table of the first children alone.  Only
     ``rows2[:seg2[2k]]`` is defined: the CPU form fills the rest with -1, the kernels leave it alone.
     ``out=(rows2, seg2)`` receives the result."""
-    if bins.dtype != torch.uint8 or bins.dim() != 2 or bins.shape[1] < 1:
-        raise ValueError("bins must be uint8 [n, F] with F >= 1")
-    if rows.dtype != torch.int32 or rows.dim() != 1 or seg.dtype != torch.int64 or seg.dim() != 1 or seg.numel() < 1:
-        raise ValueError("rows must be int32 [m] and seg int64 [k + 1]")
-    (n, F), m, k = bins.shape, rows.numel(), seg.numel() - 1
+    n, F, m, k = gbdt_args.partition(bins, rows, seg, feature, threshold, first_right)
     if first_right is None:
         first_right = torch.zeros(k, dtype=torch.int32, device=bins.device)
-    if k > 2048 or any(t.dtype != torch.int32 or tuple(t.shape) != (k,) for t in (feature, threshold, first_right)):
-        raise ValueError("feature, threshold and first_right must be int32 [k] with k <= 2048")
     if bins.is_cuda:
         from ..ops import device_ops
         return device_ops.gbdt_partition(bins.contiguous(), rows.contiguous(), seg.contiguous(), feature.contiguous(),
@@ -193,14 +169,10 @@ def gbdt_hist_subtract_torch(parent: torch.Tensor, small: torch.Tensor, parent_o
     int64 ``[k, F, B, 2]``, ``small`` int64 ``[kp, F, B, 2]``, ``parent_of`` int32 ``[kp]``; a ``parent_of[p]``
     outside ``[0, k)`` reads a zero histogram.  Histograms are exact integer sums, so this is the other
     child's histogram bit for bit."""
-    if parent.dtype != torch.int64 or parent.dim() != 4 or parent.shape[3] != 2 or small.dtype != torch.int64 or \
-            small.dim() != 4 or small.shape[1:] != parent.shape[1:] or parent_of.dtype != torch.int32 or \
-            tuple(parent_of.shape) != (small.shape[0],):
-        raise ValueError("parent must be int64 [k, F, B, 2], small int64 [kp, F, B, 2] and parent_of int32 [kp]")
+    k = gbdt_args.subtract(parent, small, parent_of)[0]
     if parent.is_cuda:
         from ..ops import device_ops
         return device_ops.gbdt_hist_subtract(parent.contiguous(), small.contiguous(), parent_of.contiguous(), out=out)
-    k = parent.shape[0]
     j = parent_of.to(torch.int64)
     inside = (j >= 0) & (j < k)
     zero = torch.zeros((1,) + tuple(parent.shape[1:]), dtype=torch.int64)
@@ -225,6 +197,8 @@ def _allreduce(comm, t: torch.Tensor, operand, operator) -> torch.Tensor:
     return t
 
 
+
+
 def gbdt_level_rows(node_of: torch.Tensor, slot_of_node: torch.Tensor, k: int):
     """``(rows, seg)`` of a level: the rows whose node has a slot, grouped by slot in ascending row
     order (torch's stable sort: K9's count / scatter halves move token rows by an id per assignment and
@@ -237,6 +211,125 @@ def gbdt_level_rows(node_of: torch.Tensor, slot_of_node: torch.Tensor, k: int):
     seg = torch.zeros(k + 1, dtype=torch.int64, device=node_of.device)
     seg[1:] = torch.cumsum(counts, 0)
     return order.to(torch.int32), seg
+
+
+def grow_level(tree: Tree, nodes: List[int], rec, sg: int, sh: int, lam: float, lr: float, last: bool) -> List[int]:
+    """Grow ``tree`` by one level on the host: ``nodes[i]`` is the tree node of histogram slot i and ``rec``
+    the split record as lists (:class:`GbdtSplit`'s fields, slot i of each).  Every node takes its leaf
+    value; it splits unless the level is the ``last``, ``H < 2`` or the record has no split (``f < 0``).
+    The nodes are taken in ascending order whatever their slots, so the children are numbered the same
+    for every grouping.  Returns the new frontier, empty when no node split."""
+    frontier = []
+    for i in sorted(range(len(nodes)), key=nodes.__getitem__):
+        f, t = rec[1][i], rec[2][i]
+        G, H = math.ldexp(rec[5][i], -sg), math.ldexp(rec[6][i], -sh)
+        tree.value[nodes[i]] = -G / (H + lam) * lr
+        if last or H < 2 or f < 0:
+            continue
+        left = tree.split(nodes[i], f, t)
+        frontier += [left, left + 1]
+    return frontier
+
+
+def move_rows(bins: torch.Tensor, node_of: torch.Tensor, tree: Tree, nodes: List[int]) -> torch.Tensor:
+    """The elementwise move of a level: a row of a node of ``nodes`` that split goes to the left child if
+    ``bin <= threshold``, else to the right one (a missing-value bin goes right); every other row stays."""
+    size = max(nodes) + 1                                   # the tree before this level grew
+    feat_of, thr_of, left_of = [-1] * size, [0] * size, [0] * size
+    for nd in nodes:
+        if tree.left[nd] >= 0:
+            feat_of[nd], thr_of[nd], left_of[nd] = tree.feature[nd], tree.threshold[nd], tree.left[nd]
+    feat_of, thr_of, left_of = (torch.tensor(t, dtype=torch.int64).to(bins.device) for t in (feat_of, thr_of, left_of))
+    f_row = feat_of[node_of]
+    b_row = bins.gather(1, f_row.clamp(min=0)[:, None])[:, 0].to(torch.int64)
+    child = left_of[node_of] + (b_row > thr_of[node_of]).to(torch.int64)
+    return torch.where(f_row >= 0, child, node_of)
+
+
+def next_segments(nodes: List[int], left: List[int], first_right: List[int]):
+    """The partition level's table after a partition, on the host: ``nodes[i]`` is the tree node of segment
+    i of k, ``left`` the grown tree's left children (-1: a final leaf, its rows were dropped),
+    ``first_right[i]`` whether segment i's right child stands first.  Returns ``(parents, take,
+    next_nodes)``: the segments that split, the entries of ``seg2`` that are the next table (the parents'
+    first children, their second children, the end; the segments between are empty, so the table is
+    contiguous and ``take[:kp + 1]`` is the table of the first children alone) and the tree node of every
+    next segment."""
+    k = len(nodes)
+    parents = [i for i in range(k) if left[nodes[i]] >= 0]
+    take = parents + [k + i for i in parents] + [2 * k]
+    first = [left[nodes[i]] + first_right[i] for i in parents]
+    second = [left[nodes[i]] + 1 - first_right[i] for i in parents]
+    return parents, take, first + second
+
+
+class _Levels:
+    """How a tree's rows are grouped by node, level after level.  ``histograms`` gives the level's job-wide
+    histograms and the tree node of every histogram slot; ``advance`` moves to the next level from the
+    grown tree and the split record (lists)."""
+
+    def __init__(self, comm, bins: torch.Tensor, gh: torch.Tensor, B: int):
+        self.comm, self.bins, self.gh, self.B = comm, bins, gh, B
+        self.nodes = [0]
+
+    def _job_hist(self, rows, seg, out=None):
+        hist = gbdt_hist_torch(self.bins, self.gh, rows, seg, self.B, out=out)
+        _allreduce(self.comm, hist.view(-1), Operands.LONG_OPERAND(), Operators.Long.SUM)
+        return hist
+
+
+class _SortLevels(_Levels):
+    """Every level sorts all rows by node (:func:`gbdt_level_rows`); the slots are the frontier in order."""
+
+    def histograms(self, tree: Tree, node_of: torch.Tensor):
+        k = len(self.nodes)
+        slot_of_node = torch.full((len(tree.value),), -1, dtype=torch.int64)
+        slot_of_node[self.nodes] = torch.arange(k)
+        return self._job_hist(*gbdt_level_rows(node_of, slot_of_node.to(node_of.device), k)), self.nodes
+
+    def advance(self, tree: Tree, rec) -> None:
+        self.nodes = [c for nd in self.nodes if tree.left[nd] >= 0 for c in (tree.left[nd], tree.right[nd])]
+
+
+class _PartitionLevels(_Levels):
+    """The rows stay grouped from level to level: every segment is split in two by
+    :func:`gbdt_partition_torch` (K17) into the other of two row buffers, and :func:`next_segments` says
+    which entries of ``seg2`` are the next table.  With ``subtract`` the child with the smaller hessian mass
+    stands first, only the first children are histogrammed and allreduced, and every sibling is parent -
+    child."""
+
+    def __init__(self, comm, bins, gh, B, subtract: bool):
+        super().__init__(comm, bins, gh, B)
+        n, dev = bins.shape[0], bins.device
+        self.subtract = subtract
+        self.rows = torch.arange(n, dtype=torch.int32, device=dev)
+        self.spare = torch.empty(n, dtype=torch.int32, device=dev)      # the two row buffers take turns
+        self.seg = torch.tensor([0, n], dtype=torch.int64, device=dev)
+        self.parents, self.hist = [], None                  # of the level before: what the siblings are taken from
+
+    def histograms(self, tree: Tree, node_of: torch.Tensor):
+        kp = len(self.parents)
+        if self.subtract and kp:
+            both = torch.empty((2 * kp,) + tuple(self.hist.shape[1:]), dtype=torch.int64, device=self.bins.device)
+            self._job_hist(self.rows, self.seg[:kp + 1], out=both[:kp])
+            parent_of = torch.tensor(self.parents, dtype=torch.int32, device=self.bins.device)
+            gbdt_hist_subtract_torch(self.hist, both[:kp], parent_of, out=both[kp:])
+            self.hist = both
+        else:
+            self.hist = self._job_hist(self.rows, self.seg)
+        return self.hist, self.nodes
+
+    def advance(self, tree: Tree, rec) -> None:
+        k, dev = len(self.nodes), self.bins.device
+        feature = [tree.feature[nd] for nd in self.nodes]   # -1: a final leaf
+        # right first iff it has the smaller hessian mass, by the allreduced record: the same on every rank
+        first_right = [int(self.subtract and f >= 0 and rec[6][i] - rec[4][i] < rec[4][i])
+                       for i, f in enumerate(feature)]
+        up = torch.tensor([feature, [tree.threshold[nd] for nd in self.nodes], first_right], dtype=torch.int32).to(dev)
+        seg2 = torch.empty(2 * k + 1, dtype=torch.int64, device=dev)
+        gbdt_partition_torch(self.bins, self.rows, self.seg, up[0], up[1], up[2], out=(self.spare, seg2))
+        self.rows, self.spare = self.spare, self.rows
+        self.parents, take, self.nodes = next_segments(self.nodes, tree.left, first_right)
+        self.seg = seg2[torch.tensor(take).to(dev)]
 
 
 def train_gbdt_quantized(comm, bins: torch.Tensor, y: torch.Tensor, B: int, trees: int = 5, depth: int = 3,
@@ -261,9 +354,8 @@ def train_gbdt_quantized(comm, bins: torch.Tensor, y: torch.Tensor, B: int, tree
         raise ValueError(f"level {level!r} must be 'sort' or 'partition'")
     if subtract and level != "partition":
         raise ValueError("subtract=True needs level='partition'")
-    part = level == "partition"
     dev = bins.device
-    n, F = bins.shape
+    n = bins.shape[0]
     y = y.to(device=dev, dtype=torch.float64)
     pred = torch.zeros(n, dtype=torch.float64, device=dev)
     h = torch.ones(n, dtype=torch.float32, device=dev)
@@ -275,76 +367,17 @@ def train_gbdt_quantized(comm, bins: torch.Tensor, y: torch.Tensor, B: int, tree
         top = _allreduce(comm, top, Operands.DOUBLE_OPERAND(), Operators.Double.MAX).tolist()
         sg, sh = gbdt_shift(top[0]), gbdt_shift(top[1])
         gh = gbdt_quantize_torch(g, h, sg, sh)
+        levels = _PartitionLevels(comm, bins, gh, B, subtract) if level == "partition" else \
+            _SortLevels(comm, bins, gh, B)
         node_of = torch.zeros(n, dtype=torch.int64, device=dev)
         tree = Tree([-1], [-1], [-1], [-1], [0.0])
-        frontier = [0]
-        seg_nodes = [0]                                   # partition: the tree node of every segment
-        if part:
-            rows, spare = torch.arange(n, dtype=torch.int32, device=dev), torch.empty(n, dtype=torch.int32, device=dev)
-            seg = torch.tensor([0, n], dtype=torch.int64, device=dev)
-        hist, parents = None, []
         for level_no in range(depth + 1):
-            k = len(frontier)
-            if not part:
-                slot_of_node = torch.full((len(tree.value),), -1, dtype=torch.int64)
-                slot_of_node[frontier] = torch.arange(k)
-                rows, seg = gbdt_level_rows(node_of, slot_of_node.to(dev), k)
-            if subtract and parents:
-                kp = len(parents)
-                both = torch.empty((2 * kp,) + tuple(hist.shape[1:]), dtype=torch.int64, device=dev)
-                gbdt_hist_torch(bins, gh, rows, seg[:kp + 1], B, out=both[:kp])
-                _allreduce(comm, both[:kp].view(-1), Operands.LONG_OPERAND(), Operators.Long.SUM)
-                gbdt_hist_subtract_torch(hist, both[:kp], torch.tensor(parents, dtype=torch.int32, device=dev),
-                                         out=both[kp:])
-                hist = both
-            else:
-                hist = gbdt_hist_torch(bins, gh, rows, seg, B)
-                _allreduce(comm, hist.view(-1), Operands.LONG_OPERAND(), Operators.Long.SUM)
-            best = gbdt_split_torch(hist, sg, sh, lam)
-            rec = [t.tolist() for t in best]
-            feat_of = torch.full((len(tree.value),), -1, dtype=torch.int64)
-            thr_of = torch.zeros(len(tree.value), dtype=torch.int64)
-            left_of = torch.zeros(len(tree.value), dtype=torch.int64)
-            seg_of = {nd: i for i, nd in enumerate(seg_nodes)} if part else {nd: i for i, nd in enumerate(frontier)}
-            new_frontier = []
-            for nd in frontier:
-                i = seg_of[nd]
-                f, t = rec[1][i], rec[2][i]
-                G, H = math.ldexp(rec[5][i], -sg), math.ldexp(rec[6][i], -sh)
-                tree.value[nd] = -G / (H + lam) * lr
-                if level_no == depth or H < 2 or f < 0:
-                    continue
-                li = len(tree.value)
-                for _ in range(2):
-                    tree.feature.append(-1)
-                    tree.threshold.append(-1)
-                    tree.left.append(-1)
-                    tree.right.append(-1)
-                    tree.value.append(0.0)
-                tree.feature[nd], tree.threshold[nd], tree.left[nd], tree.right[nd] = f, t, li, li + 1
-                feat_of[nd], thr_of[nd], left_of[nd] = f, t, li
-                new_frontier += [li, li + 1]
-            if not new_frontier:
+            hist, nodes = levels.histograms(tree, node_of)
+            rec = [t.tolist() for t in gbdt_split_torch(hist, sg, sh, lam)]
+            if not grow_level(tree, nodes, rec, sg, sh, lam, lr, last=level_no == depth):
                 break
-            if part:
-                # per segment: the split (-1: a final leaf) and which child stands first
-                sf = [tree.feature[nd] for nd in seg_nodes]
-                fr = [int(subtract and f >= 0 and rec[6][i] - rec[4][i] < rec[4][i]) for i, f in enumerate(sf)]
-                up = torch.tensor([sf, [tree.threshold[nd] for nd in seg_nodes], fr], dtype=torch.int32).to(dev)
-                seg2 = torch.empty(2 * k + 1, dtype=torch.int64, device=dev)
-                gbdt_partition_torch(bins, rows, seg, up[0], up[1], up[2], out=(spare, seg2))
-                rows, spare = spare, rows
-                parents = [i for i, f in enumerate(sf) if f >= 0]
-                seg = seg2[torch.tensor(parents + [k + i for i in parents] + [2 * k]).to(dev)]
-                seg_nodes = [tree.left[seg_nodes[i]] + fr[i] for i in parents] + \
-                            [tree.left[seg_nodes[i]] + 1 - fr[i] for i in parents]
-            feat_of, thr_of, left_of = feat_of.to(dev), thr_of.to(dev), left_of.to(dev)
-            f_row = feat_of[node_of]
-            moves = f_row >= 0
-            b_row = bins.gather(1, f_row.clamp(min=0)[:, None])[:, 0].to(torch.int64)
-            child = left_of[node_of] + (b_row > thr_of[node_of]).to(torch.int64)
-            node_of = torch.where(moves, child, node_of)
-            frontier = new_frontier
+            levels.advance(tree, rec)
+            node_of = move_rows(bins, node_of, tree, nodes)
         pred += torch.tensor(tree.value, dtype=torch.float64, device=dev)[node_of]
         out.append(tree)
     return out

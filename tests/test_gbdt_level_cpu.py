@@ -73,6 +73,29 @@ def test_parent_minus_first_children_is_the_histogram_of_the_second_children():
                                              torch.tensor([1], dtype=torch.int32)).any()
 
 
+def test_the_next_table_is_the_children_of_the_segments_that_split():
+    """Segment 1 of 3 is a final leaf, segment 2 puts its right child first: the partition's host
+    bookkeeping alone, against the definition of the partition."""
+    nodes, left = [3, 4, 6], [1, 3, -1, 7, -1, -1, 9, -1, -1, -1, -1]           # tree nodes 3 and 6 split
+    feature, first_right = [1, -1, 0], [0, 0, 1]
+    parents, take, next_nodes = gbdt.next_segments(nodes, left, first_right)
+    assert (parents, take, next_nodes) == ([0, 2], [0, 2, 3, 5, 6], [7, 10, 8, 9])
+    bins, _, rows, seg = cases.hist_case(60, 2, 16, 3)
+    i32 = dict(dtype=torch.int32)
+    rows2, seg2 = gbdt.gbdt_partition_torch(bins, rows, seg, torch.tensor(feature, **i32), torch.full((3,), 7, **i32),
+                                            torch.tensor(first_right, **i32))
+    table = seg2[torch.tensor(take)].tolist()
+    kp, s2 = len(parents), seg2.tolist()
+    assert table == sorted(table) and table[0] == 0 and table[-1] == s2[-1] and len(set(table)) == 2 * kp + 1
+    # segment j of the table holds the rows the definition gives child j: first children, then second ones
+    for j, (p, second) in enumerate([(p, 0) for p in parents] + [(p, 3) for p in parents]):
+        assert (table[j], table[j + 1]) == (s2[second + p], s2[second + p + 1])
+        went_right = bins[rows2[table[j]:table[j + 1]].long(), feature[p]] > 7
+        assert bool((went_right == (next_nodes[j] == left[nodes[p]] + 1)).all())
+    # the first kp + 1 entries are the table of the first children alone
+    assert table[:kp + 1] == [s2[p] for p in parents] + [s2[parents[-1] + 1]]
+
+
 def _trees(comm, level="sort", subtract=False):
     Bq, y = cases.model_data()
     p, r = (comm.getSlaveNum(), comm.getRank()) if comm is not None else (1, 0)

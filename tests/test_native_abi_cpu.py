@@ -300,3 +300,20 @@ def test_enums_and_error_codes_equal_their_python_mirrors():
             native.check(code, "x")
     from mp4x.ops import device_ops
     assert int(re.search(r"^#define MP4X_MAX_NIN (\d+)$", _read("ops.h"), re.M).group(1)) == device_ops.MAX_NIN
+
+
+def test_gbdt_limits_equal_the_map_headers():
+    """The ``constexpr`` lines of the GBDT limits, read from the two map headers; ``kMaxParents`` is stated
+    as half of ``kMaxNodes`` there and is resolved the same way."""
+    from mp4x.ops import gbdt_args
+    kernels = os.path.join(ROOT, "csrc", "kernels")
+
+    def constexpr(header, name):
+        with open(os.path.join(kernels, header)) as f:
+            return re.search(rf"^constexpr int {name} = ([^;]+);", f.read(), re.M).group(1)
+
+    native = {name: int(constexpr("gbdt_hist_map.hpp", name)) for name in ("kMaxNodes", "kMaxBins", "kMaxShift")}
+    assert constexpr("gbdt_part_map.hpp", "kMaxParents") == "gm::kMaxNodes / 2"
+    native["kMaxParents"] = native["kMaxNodes"] // 2
+    assert native == {"kMaxNodes": gbdt_args.MAX_NODES, "kMaxBins": gbdt_args.MAX_BINS,
+                      "kMaxShift": gbdt_args.MAX_SHIFT, "kMaxParents": gbdt_args.MAX_PARENTS}
