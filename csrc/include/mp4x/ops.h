@@ -399,6 +399,25 @@ int mp4x_gbdt_partition(const uint8_t* bins, const int32_t* rows, const int64_t*
 int mp4x_gbdt_hist_subtract(const int64_t* parent, const int64_t* small, const int32_t* parent_of, int k, int kp,
                             int64_t cells, int64_t* large, void* stream);
 
+// ---------------------------------------------------------------- K18 GBDT forest prediction
+// pred[r] = init[r] (+0.0 when init is null) + the values of the nodes the walks of row r end on, one
+// f64 addition a tree in the order t = 0 .. T-1, so the sum has the same bits as the same additions on
+// the host.  bins u8[n, F] row-major (no alignment is assumed, F >= 1); nodes int32[N, 4] = (feature,
+// threshold, left, right) with children relative to the tree's first node, 16-byte aligned; value
+// f64[N]; tree_off int32[T + 1]: tree t owns the nodes [o[t], o[t+1]) with o[0] = 0 and o[t+1] =
+// max(o[t], min(tree_off[t+1], N)).  The forest is read on the device only and any bits are legal
+// (csrc/kernels/gbdt_walk_map.hpp): a walk starts at node 0 and takes `steps` steps; a node is inner iff
+// 0 <= feature < F and both children are in [0, size of the tree); there the row moves right iff
+// bins[r, feature] > threshold (any int32 threshold), else left; at any other node it stays.  A tree
+// without nodes adds nothing.  leaf (may be null) int32[n, T]: the node every walk ended on, -1 for a
+// tree without nodes.  init (may be null) f64[n]; pred f64[n] may be init: a row is read and written
+// by one thread.  0 <= n, T, N < 2^31, n * T < 2^31 with leaf, 0 <= steps <= 64, F >= 1, pred and init
+// 8-byte, leaf and tree_off 4-byte aligned, else MP4X_E_BADARG before any launch; n == 0 launches
+// nothing.  One launch, no atomics, no allocation and no host read: recordable in a graph.
+int mp4x_gbdt_predict(const uint8_t* bins, const int32_t* nodes, const double* value, const int32_t* tree_off,
+                      const double* init, int64_t n, int64_t F, int64_t T, int64_t N, int steps, double* pred,
+                      int32_t* leaf, void* stream);
+
 // ---------------------------------------------------------------- errors
 // Reads and clears this thread's last HIP error.  mp4x reports its own failures through return
 // codes; a failed HIP call must not stay "last error" for PyTorch's next kernel-launch check to

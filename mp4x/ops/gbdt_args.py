@@ -1,4 +1,4 @@
-"""The argument rules of the fixed-point GBDT ops (K16, K17) and the limits behind them, stated once:
+"""The argument rules of the fixed-point GBDT ops (K16, K17, K18) and the limits behind them, stated once:
 the definitions of :mod:`mp4x.parallel.gbdt` and the wrappers of :mod:`mp4x.ops.device_ops` both call
 the op's function here, which checks what both forms require and returns the sizes.  What only the
 device requires (GPU tensors, sizes below ``2**31``, alignment, the node caps, ``out=``) stays with the
@@ -15,6 +15,7 @@ MAX_NODES = 4096                     # kMaxNodes: a histogram table fits one blo
 MAX_PARENTS = MAX_NODES // 2         # kMaxParents: the 2k children stay a histogram table
 MAX_BINS = 256                       # kMaxBins: bins are bytes
 QMAX = 2 ** 31 - 1                   # a quantised gradient or hessian is clamped to +-QMAX
+MAX_STEPS = 64                       # kMaxSteps (gbdt_walk_map.hpp): the longest root-to-leaf path, in edges
 
 
 def shifts(*s) -> None:
@@ -74,3 +75,19 @@ def subtract(parent: torch.Tensor, small: torch.Tensor, parent_of: torch.Tensor)
             tuple(parent_of.shape) != (small.shape[0],):
         raise ValueError("parent must be int64 [k, F, B, 2], small int64 [kp, F, B, 2] and parent_of int32 [kp]")
     return parent.shape[0], small.shape[0], parent.shape[1] * parent.shape[2]
+
+
+def predict(bins: torch.Tensor, nodes: torch.Tensor, value: torch.Tensor, tree_off: torch.Tensor, steps: int,
+            init: Optional[torch.Tensor]):
+    """``(n, F, T, N)``; ``init`` may be None (the sums start at ``+0.0``)."""
+    if bins.dtype != torch.uint8 or bins.dim() != 2 or bins.shape[1] < 1:
+        raise ValueError("bins must be uint8 [n, F] with F >= 1")
+    if nodes.dtype != torch.int32 or nodes.dim() != 2 or nodes.shape[1] != 4 or value.dtype != torch.float64 or \
+            tuple(value.shape) != (nodes.shape[0],) or tree_off.dtype != torch.int32 or tree_off.dim() != 1 or \
+            tree_off.numel() < 1:
+        raise ValueError("nodes must be int32 [N, 4], value float64 [N] and tree_off int32 [T + 1]")
+    if isinstance(steps, bool) or not isinstance(steps, int) or not 0 <= steps <= MAX_STEPS:
+        raise ValueError(f"steps {steps!r} must be an int in [0, {MAX_STEPS}]")
+    if init is not None and (init.dtype != torch.float64 or tuple(init.shape) != (bins.shape[0],)):
+        raise ValueError("init must be float64 [n]")
+    return tuple(bins.shape) + (tree_off.numel() - 1, nodes.shape[0])

@@ -1,5 +1,5 @@
-"""Histogram GBDT in exact fixed point (K16): the definitions in torch (also the CPU form) and the
-data-parallel trainer on them.
+"""Histogram GBDT in exact fixed point (K16, K17), the forest walk that applies a trained model (K18): the
+definitions in torch (also the CPU form) and the data-parallel trainer on them.
 
 Gradients and hessians are quantised once a tree to int32 with a shift both sides agree on
 (:func:`gbdt_shift` of the job-wide largest magnitude), histograms are int64 sums of them and the
@@ -7,13 +7,13 @@ split search reads integer prefix sums.  Integer sums do not depend on their ord
 the same bits for every block schedule, tile size, rank count and device, the allreduce over ranks is
 an exact int64 SUM, and :func:`train_gbdt_quantized` grows bit-identical trees on 1 or p ranks, on the
 CPU or the GPU.  Every ``*_torch`` function is the definition; on GPU tensors it runs the HIP kernels
-of csrc/kernels/gbdt.hip through :mod:`mp4x.ops.device_ops` (a missing kernel is an error, there is no
+of csrc/kernels/gbdt*.hip through :mod:`mp4x.ops.device_ops` (a missing kernel is an error, there is no
 torch fallback on the GPU).
 """
 from __future__ import annotations
 
 import math
-from typing import List
+from typing import List, NamedTuple, Optional, Sequence
 
 import torch
 
@@ -22,7 +22,7 @@ from ..operands import Operands
 from ..operators import Operators
 from ..ops import gbdt_args
 from ..ops.device_ops import GbdtSplit
-from ..ops.gbdt_args import MAX_SHIFT, QMAX
+from ..ops.gbdt_args import MAX_SHIFT, MAX_STEPS, QMAX
 
 MIN_GAIN = 1e-12
 
@@ -183,6 +183,114 @@ def gbdt_hist_subtract_torch(parent: torch.Tensor, small: torch.Tensor, parent_o
     return large
 
 
+# ---------------------------------------------------------------- the forest walk (K18)
+class GbdtForest(NamedTuple):
+    nodes: torch.Tensor       # int32 [N, 4]: (feature, threshold, left, right), children relative to the tree's first
+    #                           node; a leaf has feature -1
+    value: torch.Tensor       # float64 [N]: the exact bits of Tree.value, inner nodes too
+    tree_off: torch.Tensor    # int32 [T + 1] from 0
+    steps: int                # the longest root-to-leaf path of the forest, in edges
+
+
+def _tree_depth(tree: Tree, t: int) -> int:
+    """The longest path below node 0 in edges; ValueError for a child outside the tree or a cycle."""
+    size = len(tree.value)
+    kids = []
+    for j in range(size):
+        if tree.left[j] < 0:
+            kids.append(())
+            continue
+        if not (0 <= tree.left[j] < size and 0 <= tree.right[j] < size and tree.feature[j] >= 0):
+            raise ValueError(f"tree {t}: node {j} has a child outside the tree's {size} nodes or no feature")
+        kids.append((tree.left[j], tree.right[j]))
+    depth = [-1] * size                                     # -1: not seen, -2: on the path being walked
+    stack = [0] if size else []
+    while stack:
+        j = stack[-1]
+        if depth[j] == -1:
+            depth[j] = -2
+            for c in kids[j]:
+                if depth[c] == -2:
+                    raise ValueError(f"tree {t}: a cycle through node {c}")
+                if depth[c] == -1:
+                    stack.append(c)
+        else:
+            stack.pop()
+            if depth[j] == -2:
+                depth[j] = 1 + max(depth[c] for c in kids[j]) if kids[j] else 0
+    return depth[0] if size else 0
+
+
+def pack_forest(trees: Sequence[Tree], device=None) -> GbdtForest:
+    """The trees as the tensors :func:`gbdt_predict_torch` walks, on ``device``.  A node of a
+    :class:`~mp4x.models.gbdt.Tree` is inner iff ``left >= 0``; ValueError for an inner node with a child
+    outside its tree or without a feature, for a cycle and for a path longer than ``MAX_STEPS`` edges."""
+    rows, value, off, steps = [], [], [0], 0
+    for t, tree in enumerate(trees):
+        steps = max(steps, _tree_depth(tree, t))
+        if steps > MAX_STEPS:
+            raise ValueError(f"tree {t}: a path of {steps} edges, at most {MAX_STEPS}")
+        for j in range(len(tree.value)):
+            inner = tree.left[j] >= 0
+            rows.append((tree.feature[j] if inner else -1, tree.threshold[j], tree.left[j], tree.right[j]))
+        value += tree.value
+        off.append(len(value))
+    if len(value) >= 2 ** 31:
+        raise ValueError("a forest holds fewer than 2**31 nodes")
+    return GbdtForest(torch.tensor(rows, dtype=torch.int32).reshape(-1, 4).to(device),
+                      torch.tensor(value, dtype=torch.float64).to(device), torch.tensor(off, dtype=torch.int32).to(device),
+                      steps)
+
+
+def gbdt_predict_torch(bins: torch.Tensor, forest: GbdtForest, init: Optional[torch.Tensor] = None, leaves: bool = False,
+                       out=None):
+    """``pred`` float64 ``[n]``, and ``leaf`` int32 ``[n, T]`` with ``leaves``: the forest applied to the rows of
+    ``bins`` uint8 ``[n, F]``.  The tensors of ``forest`` may hold any bits.  Tree t owns the nodes ``[o[t], o[t +
+    1])`` with ``o[0] = 0`` and ``o[t + 1] = max(o[t], min(tree_off[t + 1], N))``, ``size_t`` of them.  The walk of a
+    row in tree t starts at node 0 and takes exactly ``forest.steps`` steps.  Node j is inner iff ``0 <= feature <
+    F``, ``0 <= left < size_t`` and ``0 <= right < size_t``; there the row moves to ``right`` iff ``int(bins[r,
+    feature]) > threshold`` (any int32 threshold; the trainer's rule, a missing-value bin goes right), else to
+    ``left``; at any other node it stays.  ``pred[r]`` starts as ``init[r]`` (float64 ``[n]``) or ``+0.0``; the trees
+    are taken in ascending order and a tree with nodes adds ``value[o[t] + j]``, one float64 addition, and gives
+    ``leaf[r, t] = j``; a tree without nodes adds nothing and gives -1.  ``T = 0`` returns ``init`` bit for bit.
+    The order of the sum is fixed, so this form, the kernel and ``sum(tree.predict_bins(...))`` in tree order
+    agree bit for bit.  ``out`` receives ``pred`` (the pair ``(pred, leaf)`` with ``leaves``); ``pred`` may be
+    ``init``."""
+    n, F, T, N = gbdt_args.predict(bins, forest.nodes, forest.value, forest.tree_off, forest.steps, init)
+    if bins.is_cuda:
+        from ..ops import device_ops
+        return device_ops.gbdt_predict(bins.contiguous(), forest.nodes.contiguous(), forest.value.contiguous(),
+                                       forest.tree_off.contiguous(), forest.steps,
+                                       None if init is None else init.contiguous(), leaves=leaves, out=out)
+    o = _clamped_bounds(forest.tree_off, N)
+    pred = torch.zeros(n, dtype=torch.float64) if init is None else init.clone()
+    leaf = torch.full((n, T), -1, dtype=torch.int32)
+    for t in range(T):
+        size = o[t + 1] - o[t]
+        if size == 0:
+            continue
+        f, thr, left, right = forest.nodes[o[t]:o[t + 1]].to(torch.int64).unbind(1)
+        inner = (f >= 0) & (f < F) & (left >= 0) & (left < size) & (right >= 0) & (right < size)
+        j = torch.zeros(n, dtype=torch.int64)
+        for _ in range(forest.steps):
+            b = bins.gather(1, torch.where(inner, f, torch.zeros_like(f))[j][:, None])[:, 0].to(torch.int64)
+            j = torch.where(inner[j], torch.where(b > thr[j], right[j], left[j]), j)
+        pred = pred + forest.value[o[t]:o[t + 1]][j]
+        leaf[:, t] = j.to(torch.int32)
+    if out is not None:
+        outs = tuple(out) if leaves else (out,)
+        outs[0].copy_(pred)
+        if leaves:
+            outs[1].copy_(leaf)
+        return outs if leaves else outs[0]
+    return (pred, leaf) if leaves else pred
+
+
+def predict_gbdt(trees: Sequence[Tree], bins: torch.Tensor, init: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The sum of the trees' predictions for the rows of ``bins`` uint8 ``[n, F]``, on the device of ``bins``."""
+    return gbdt_predict_torch(bins, pack_forest(trees, bins.device), init=init)
+
+
 # ---------------------------------------------------------------- the trainer
 def _allreduce(comm, t: torch.Tensor, operand, operator) -> torch.Tensor:
     """In-place allreduce of a flat tensor over the job: the device engine for a GPU tensor, the host
@@ -333,7 +441,8 @@ class _PartitionLevels(_Levels):
 
 
 def train_gbdt_quantized(comm, bins: torch.Tensor, y: torch.Tensor, B: int, trees: int = 5, depth: int = 3,
-                         lr: float = 0.3, lam: float = 1.0, level: str = "sort", subtract: bool = False) -> List[Tree]:
+                         lr: float = 0.3, lam: float = 1.0, level: str = "sort", subtract: bool = False,
+                         update: str = "rows") -> List[Tree]:
     """:func:`mp4x.models.gbdt.train_gbdt` on fixed-point statistics: ``bins`` uint8 ``[n, F]`` and ``y``
     ``[n]`` are this rank's rows, torch tensors on the CPU or the GPU.  Squared loss: ``g = float32(pred -
     y)``, ``h = 1``.  Per tree one allreduce MAX of ``(max|g|, max|h|)`` fixes the shifts and the rows are
@@ -349,11 +458,21 @@ def train_gbdt_quantized(comm, bins: torch.Tensor, y: torch.Tensor, B: int, tree
     (``level="partition"`` only) puts the child with the smaller hessian mass first (right iff ``H - HL <
     HL`` of the allreduced record: the same on every rank), histograms and allreduces the first children
     alone and takes every sibling as parent - child (:func:`gbdt_hist_subtract_torch`), exactly.  Both
-    grow the default's trees bit for bit."""
+    grow the default's trees bit for bit.
+
+    ``update`` is how a finished tree reaches ``pred``: ``"rows"`` moves ``node_of`` elementwise after every level
+    (:func:`move_rows`) and adds ``value[node_of]``; ``"walk"`` (``level="partition"`` only, which never reads
+    ``node_of``) keeps no ``node_of`` and walks the finished tree once with :func:`gbdt_predict_torch` (K18).  The
+    walk ends on the leaf ``node_of`` would hold and adds the same float64, so the trees are the same bit for
+    bit."""
     if level not in ("sort", "partition"):
         raise ValueError(f"level {level!r} must be 'sort' or 'partition'")
     if subtract and level != "partition":
         raise ValueError("subtract=True needs level='partition'")
+    if update not in ("rows", "walk"):
+        raise ValueError(f"update {update!r} must be 'rows' or 'walk'")
+    if update == "walk" and level != "partition":
+        raise ValueError("update='walk' needs level='partition'")
     dev = bins.device
     n = bins.shape[0]
     y = y.to(device=dev, dtype=torch.float64)
@@ -369,7 +488,7 @@ def train_gbdt_quantized(comm, bins: torch.Tensor, y: torch.Tensor, B: int, tree
         gh = gbdt_quantize_torch(g, h, sg, sh)
         levels = _PartitionLevels(comm, bins, gh, B, subtract) if level == "partition" else \
             _SortLevels(comm, bins, gh, B)
-        node_of = torch.zeros(n, dtype=torch.int64, device=dev)
+        node_of = torch.zeros(n, dtype=torch.int64, device=dev) if update == "rows" else None
         tree = Tree([-1], [-1], [-1], [-1], [0.0])
         for level_no in range(depth + 1):
             hist, nodes = levels.histograms(tree, node_of)
@@ -377,7 +496,11 @@ def train_gbdt_quantized(comm, bins: torch.Tensor, y: torch.Tensor, B: int, tree
             if not grow_level(tree, nodes, rec, sg, sh, lam, lr, last=level_no == depth):
                 break
             levels.advance(tree, rec)
-            node_of = move_rows(bins, node_of, tree, nodes)
-        pred += torch.tensor(tree.value, dtype=torch.float64, device=dev)[node_of]
+            if update == "rows":
+                node_of = move_rows(bins, node_of, tree, nodes)
+        if update == "rows":
+            pred += torch.tensor(tree.value, dtype=torch.float64, device=dev)[node_of]
+        else:
+            pred = gbdt_predict_torch(bins, pack_forest([tree], dev), init=pred)
         out.append(tree)
     return out
