@@ -418,6 +418,19 @@ int mp4x_gbdt_predict(const uint8_t* bins, const int32_t* nodes, const double* v
                       const double* init, int64_t n, int64_t F, int64_t T, int64_t N, int steps, double* pred,
                       int32_t* leaf, void* stream);
 
+// ---------------------------------------------------------------- K19 GBDT feature binning
+// bins[r, f] = missing if X[r, f] is NaN, else pos of the fixed search (csrc/kernels/gbdt_bin_map.hpp): pos
+// = 0; for s in (128, 64, .., 1): if pos + s <= c and edges[f, pos + s - 1] <= x then pos += s, with c =
+// clamp(cnt[f], 0, E) and x = X[r, f] widened to f32; the compare is IEEE (denormals count, -0 == +0, a NaN
+// edge is never <= x) whatever the compile's float mode.  For ascending edges pos is the number of edges
+// <= x.  X [n, F] row-major of dtype MP4X_F32, MP4X_F16 or MP4X_BF16, aligned to its element; edges f32[F,
+// E] and cnt int32[F] in device memory, read there only, any bits are legal; bins u8[n, F].  0 <= E <= 255,
+// 0 <= missing <= 255, 0 <= n, F < 2^31 and ceil(F / 64) * ceil(n / 4096) < 2^31, else MP4X_E_BADARG
+// before any launch; edges may be null when E == 0; n == 0 or F == 0 launches nothing.  One launch, no
+// atomics, no allocation and no host read: recordable in a graph.
+int mp4x_gbdt_bin(const void* X, int dtype, const float* edges, const int32_t* cnt, int64_t n, int64_t F, int E,
+                  int missing, uint8_t* bins, void* stream);
+
 // ---------------------------------------------------------------- errors
 // Reads and clears this thread's last HIP error.  mp4x reports its own failures through return
 // codes; a failed HIP call must not stay "last error" for PyTorch's next kernel-launch check to

@@ -836,6 +836,24 @@ def gbdt_predict(bins: torch.Tensor, nodes: torch.Tensor, value: torch.Tensor, t
     return (pred, leaf) if leaves else pred
 
 
+def gbdt_bin(X: torch.Tensor, edges: torch.Tensor, cnt: torch.Tensor, missing: int = 255,
+             out: Optional[torch.Tensor] = None, stream=None) -> torch.Tensor:
+    """K19: ``bins`` uint8 ``[n, F]`` of the float features ``X`` ``[n, F]`` (float32, float16 or bfloat16; the
+    definition: :func:`mp4x.parallel.gbdt.gbdt_bin_torch`): the position the fixed eight-step search over
+    ``edges[f, :clamp(cnt[f], 0, E)]`` ends on, ``missing`` for a NaN.  ``edges`` float32 ``[F, E]`` and ``cnt`` int32
+    ``[F]`` are read on the device only, any bits are legal."""
+    _dev_check(X, edges, cnt, out)
+    n, F, E = gbdt_args.bin(X, edges, cnt, missing)
+    if n >= 2 ** 31 or F >= 2 ** 31 or -(-F // 64) * -(-n // 4096) >= 2 ** 31:
+        raise ValueError("gbdt_bin: n, F and ceil(F / 64) * ceil(n / 4096) must be below 2**31")
+    out = _gbdt_out("gbdt_bin", out, (n, F), torch.uint8, X.device)
+    live = bool(n and F)
+    check(native.hip().mp4x_gbdt_bin(X.data_ptr() if live else None, int(dtype_of_torch(X.dtype)),
+                                     edges.data_ptr() if F * E else None, cnt.data_ptr() if F else None, n, F, E,
+                                     missing, out.data_ptr() if live else None, stream_ptr(stream)), "mp4x_gbdt_bin")
+    return out
+
+
 MOE_COMBINE_BWD_MAX_TOP_K = 16       # csrc/kernels/moe.hip: kMoeBwdMaxK
 
 

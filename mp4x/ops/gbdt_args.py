@@ -1,4 +1,4 @@
-"""The argument rules of the fixed-point GBDT ops (K16, K17, K18) and the limits behind them, stated once:
+"""The argument rules of the fixed-point GBDT ops (K16, K17, K18, K19) and the limits behind them, stated once:
 the definitions of :mod:`mp4x.parallel.gbdt` and the wrappers of :mod:`mp4x.ops.device_ops` both call
 the op's function here, which checks what both forms require and returns the sizes.  What only the
 device requires (GPU tensors, sizes below ``2**31``, alignment, the node caps, ``out=``) stays with the
@@ -16,6 +16,7 @@ MAX_PARENTS = MAX_NODES // 2         # kMaxParents: the 2k children stay a histo
 MAX_BINS = 256                       # kMaxBins: bins are bytes
 QMAX = 2 ** 31 - 1                   # a quantised gradient or hessian is clamped to +-QMAX
 MAX_STEPS = 64                       # kMaxSteps (gbdt_walk_map.hpp): the longest root-to-leaf path, in edges
+MAX_EDGES = 255                      # kMaxEdges (gbdt_bin_map.hpp): a position among the edges is a byte
 
 
 def shifts(*s) -> None:
@@ -91,3 +92,29 @@ def predict(bins: torch.Tensor, nodes: torch.Tensor, value: torch.Tensor, tree_o
     if init is not None and (init.dtype != torch.float64 or tuple(init.shape) != (bins.shape[0],)):
         raise ValueError("init must be float64 [n]")
     return tuple(bins.shape) + (tree_off.numel() - 1, nodes.shape[0])
+
+
+def features(X: torch.Tensor):
+    """``(n, F)``."""
+    if X.dtype not in (torch.float32, torch.float16, torch.bfloat16) or X.dim() != 2:
+        raise ValueError("X must be float32, float16 or bfloat16 [n, F]")
+    return tuple(X.shape)
+
+
+def edges(X: torch.Tensor, B: int):
+    """``(n, F)``; ``B - 1 <= MAX_EDGES``."""
+    if isinstance(B, bool) or not isinstance(B, int) or not 2 <= B <= MAX_EDGES + 1:
+        raise ValueError(f"B {B!r} must be an int in [2, {MAX_EDGES + 1}]")
+    return features(X)
+
+
+def bin(X: torch.Tensor, edges: torch.Tensor, cnt: torch.Tensor, missing: int):
+    """``(n, F, E)``."""
+    F = features(X)[1]
+    if edges.dtype != torch.float32 or edges.dim() != 2 or edges.shape[0] != F or edges.shape[1] > MAX_EDGES:
+        raise ValueError(f"edges must be float32 [F, E] with E <= {MAX_EDGES}")
+    if cnt.dtype != torch.int32 or tuple(cnt.shape) != (F,):
+        raise ValueError("cnt must be int32 [F]")
+    if isinstance(missing, bool) or not isinstance(missing, int) or not 0 <= missing <= 255:
+        raise ValueError(f"missing {missing!r} must be an int in [0, 255]")
+    return X.shape[0], F, edges.shape[1]

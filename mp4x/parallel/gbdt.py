@@ -1,5 +1,6 @@
-"""Histogram GBDT in exact fixed point (K16, K17), the forest walk that applies a trained model (K18): the
-definitions in torch (also the CPU form) and the data-parallel trainer on them.
+"""Histogram GBDT in exact fixed point (K16, K17), the forest walk that applies a trained model (K18), the
+binning of float features that both start from (K19): the definitions in torch (also the CPU form) and the
+data-parallel trainer on them.
 
 Gradients and hessians are quantised once a tree to int32 with a shift both sides agree on
 (:func:`gbdt_shift` of the job-wide largest magnitude), histograms are int64 sums of them and the
@@ -289,6 +290,110 @@ def gbdt_predict_torch(bins: torch.Tensor, forest: GbdtForest, init: Optional[to
 def predict_gbdt(trees: Sequence[Tree], bins: torch.Tensor, init: Optional[torch.Tensor] = None) -> torch.Tensor:
     """The sum of the trees' predictions for the rows of ``bins`` uint8 ``[n, F]``, on the device of ``bins``."""
     return gbdt_predict_torch(bins, pack_forest(trees, bins.device), init=init)
+
+
+# ---------------------------------------------------------------- feature binning (K19)
+_SEARCH_STEPS = (128, 64, 32, 16, 8, 4, 2, 1)
+_SORT_CHUNK = 1 << 24                 # elements one torch.sort call takes: bounds its int64 index tensor
+
+
+def gbdt_bin_torch(X: torch.Tensor, edges: torch.Tensor, cnt: torch.Tensor, missing: int = 255,
+                   out: torch.Tensor = None) -> torch.Tensor:
+    """``bins`` uint8 ``[n, F]`` of the features ``X`` ``[n, F]`` (float32, or float16 / bfloat16 widened to float32,
+    which is exact; contiguous on the GPU) under ``edges`` float32 ``[F, E]``, ``E <= MAX_EDGES`` (255), and ``cnt``
+    int32 ``[F]``.  The tensors may hold any bits.  With ``c = clamp(cnt[f], 0, E)`` and ``x = X[r, f]``::
+
+        pos = 0
+        for s in (128, 64, 32, 16, 8, 4, 2, 1):
+            if pos + s <= c and edges[f, pos + s - 1] <= x:
+                pos += s
+        bin = missing if x is NaN else pos
+
+    The compare is float32 IEEE: denormals are not flushed, ``-0.0 == +0.0``, a NaN edge is never ``<= x``, ``+-inf``
+    are ordinary values.  This fixed search is the definition, so unsorted or NaN edges have one answer too; for
+    ascending edges it is ``searchsorted(edges[f, :c], x, side="right")``, the rule of
+    :func:`mp4x.models.gbdt.quantize`.  ``pos <= c <= 255``.  A NaN lands in ``missing`` (an int in ``[0, 255]``): with
+    ``B <= 255`` bins and ``missing = 255`` the histogram skips it and the partition and the walk send it right, as
+    K16-K18 define for a bin ``>= B``; with ``B = 256`` bin 255 is an ordinary bin, shared with the largest
+    values.  ``out`` receives the result."""
+    n, F, E = gbdt_args.bin(X, edges, cnt, missing)
+    if X.is_cuda:
+        from ..ops import device_ops
+        return device_ops.gbdt_bin(X, edges.contiguous(), cnt.contiguous(), missing, out=out)
+    x = X.to(torch.float32)
+    c = cnt.clamp(0, E).to(torch.int64)[None, :]
+    pos = torch.zeros(n, F, dtype=torch.int64)
+    by_entry = edges.t()                                                          # [E, F]
+    for s in _SEARCH_STEPS if E else ():
+        entry = by_entry.gather(0, (pos + s - 1).clamp(max=E - 1))
+        pos = torch.where((pos + s <= c) & (entry <= x), pos + s, pos)
+    bins = torch.where(torch.isnan(x), torch.full_like(pos, missing), pos).to(torch.uint8)
+    if out is not None:
+        return out.copy_(bins)
+    return bins
+
+
+def _float_keys(X: torch.Tensor) -> torch.Tensor:
+    """int32 keys of the values widened to float32 whose signed order is the order of the floats: ``-0.0`` takes
+    the key of ``+0.0``, a NaN the largest int32, which is the key of no other value (``+inf``'s is below it).  Bit
+    operations only, so both devices give the same keys whatever their float modes."""
+    u = X.to(torch.float32).view(torch.int32)
+    u = torch.where(u == -2 ** 31, torch.zeros_like(u), u)
+    nan = (u & 0x7fffffff) > 0x7f800000
+    return torch.where(nan, torch.full_like(u, 2 ** 31 - 1), torch.where(u < 0, u ^ 0x7fffffff, u))
+
+
+def _key_floats(k: torch.Tensor) -> torch.Tensor:
+    """The float32 values of :func:`_float_keys`' keys (int32; none of them a NaN's)."""
+    return torch.where(k < 0, k ^ 0x7fffffff, k).view(torch.float32)
+
+
+def gbdt_edges(comm, X: torch.Tensor, B: int):
+    """``(edges float32 [F, B - 1], cnt int32 [F])``: exact quantile edges of the job's rows, the same bits for
+    every sharding of the rows over the ranks and on either device.  ``X`` ``[n, F]`` (float32, float16 or
+    bfloat16) are this rank's rows, ``2 <= B <= 256``.  Per feature, the job-wide multiset of the non-NaN values,
+    widened to float32 with ``-0.0`` taken as ``+0.0``, has ``N_f`` members; the candidate ``q = 1 .. B - 1`` is its
+    order statistic of 0-based rank ``(q * N_f) // B`` (integers, no interpolation: an input value).
+    ``edges[f, :cnt[f]]`` are the distinct candidates ascending, the rest of the row is ``+inf``; ``N_f = 0`` gives
+    ``cnt[f] = 0``.
+
+    Every rank sorts its own columns once (order-preserving int32 keys, ``torch.sort`` in feature chunks); one
+    int64 SUM allreduce gives ``N_f``; then 32 rounds of bisection on the key find all ``F * (B - 1)`` order
+    statistics at once, each round one batched ``searchsorted`` on the local columns and one int64 SUM
+    allreduce of the ``[F, B - 1]`` counts: the wanted key is the smallest ``K`` with ``count(keys <= K) >= rank +
+    1``.  Only integer counts cross ranks, so the sharding cannot show."""
+    n, F = gbdt_args.edges(X, B)
+    dev, E = X.device, B - 1
+    long_sum = (Operands.LONG_OPERAND(), Operators.Long.SUM)
+    per_call = max(1, _SORT_CHUNK // max(n, 1))
+    cols = torch.cat([torch.sort(_float_keys(X[:, f:f + per_call]).t().contiguous(), dim=1).values
+                      for f in range(0, F, per_call)]) if F else torch.empty(0, n, dtype=torch.int32, device=dev)
+    N = _allreduce(comm, (cols != 2 ** 31 - 1).sum(dim=1), *long_sum)             # [F] int64
+    rank = torch.arange(1, B, device=dev)[None, :] * N[:, None] // B              # [F, E] int64
+    lo = torch.full((F, E), -2 ** 31, dtype=torch.int64, device=dev)
+    hi = torch.full((F, E), int(_float_keys(torch.tensor([math.inf]))), dtype=torch.int64, device=dev)
+    for _ in range(32):                                                           # hi - lo < 2**32 halves to 0
+        mid = (lo + hi) >> 1
+        below = torch.searchsorted(cols, mid.to(torch.int32), right=True)         # local keys <= mid; never a NaN's
+        below = _allreduce(comm, below.to(torch.int64).view(-1), *long_sum).view(F, E)
+        found = below >= rank + 1
+        hi = torch.where(found, mid, hi)
+        lo = torch.where(found, lo, mid + 1)
+    cand = lo.to(torch.int32)                                                     # non-decreasing along q
+    first = torch.ones(F, E, dtype=torch.bool, device=dev)
+    first[:, 1:] = cand[:, 1:] != cand[:, :-1]
+    cnt = torch.where(N > 0, first.sum(dim=1), torch.zeros_like(N))
+    front = torch.sort((~first).to(torch.uint8), dim=1, stable=True).indices      # the distinct ones first, in order
+    edges = _key_floats(cand.gather(1, front))
+    edges = torch.where(torch.arange(E, device=dev)[None, :] < cnt[:, None], edges, torch.full_like(edges, math.inf))
+    return edges, cnt.to(torch.int32)
+
+
+def fit_bins(comm, X: torch.Tensor, B: int, missing: int = 255):
+    """``(bins, edges, cnt)``: :func:`gbdt_edges` of the job's rows, then :func:`gbdt_bin_torch` of this rank's, on
+    the device of ``X``: what :func:`train_gbdt_quantized` and :func:`predict_gbdt` start from."""
+    edges, cnt = gbdt_edges(comm, X, B)
+    return gbdt_bin_torch(X, edges, cnt, missing), edges, cnt
 
 
 # ---------------------------------------------------------------- the trainer
