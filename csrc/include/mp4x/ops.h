@@ -431,6 +431,20 @@ int mp4x_gbdt_predict(const uint8_t* bins, const int32_t* nodes, const double* v
 int mp4x_gbdt_bin(const void* X, int dtype, const float* edges, const int32_t* cnt, int64_t n, int64_t F, int E,
                   int missing, uint8_t* bins, void* stream);
 
+// ---------------------------------------------------------------- K20 GBDT forest prediction from float features
+// mp4x_gbdt_predict over rows of features instead of bins, in one launch and with no bin tensor.  X [n, F]
+// row-major of dtype MP4X_F32, MP4X_F16 or MP4X_BF16, aligned to its element, widened exactly to f32.  The
+// forest, the tree table, the walk, pred, leaf and init are K18's word for word but for the step: a node's
+// second field is a uint32 key K (its int32 bits) and at an inner node the row moves right iff K <=
+// xkey(X[r, feature]) compared as unsigned, xkey being the order-preserving key of
+// csrc/kernels/gbdt_bin_map.hpp for a non-NaN value and 0xfffffffe for a NaN
+// (csrc/kernels/gbdt_fwalk_map.hpp).  Any bits are legal in the forest and in X.  The limits, alignment
+// rules and return codes are mp4x_gbdt_predict's; a dtype outside the three is MP4X_E_BADARG.  One launch,
+// no atomics, no allocation and no host read: recordable in a graph.
+int mp4x_gbdt_predict_float(const void* X, int dtype, const int32_t* nodes, const double* value,
+                            const int32_t* tree_off, const double* init, int64_t n, int64_t F, int64_t T, int64_t N,
+                            int steps, double* pred, int32_t* leaf, void* stream);
+
 // ---------------------------------------------------------------- errors
 // Reads and clears this thread's last HIP error.  mp4x reports its own failures through return
 // codes; a failed HIP call must not stay "last error" for PyTorch's next kernel-launch check to

@@ -854,6 +854,31 @@ def gbdt_bin(X: torch.Tensor, edges: torch.Tensor, cnt: torch.Tensor, missing: i
     return out
 
 
+def gbdt_predict_float(X: torch.Tensor, nodes: torch.Tensor, value: torch.Tensor, tree_off: torch.Tensor, steps: int,
+                       init: Optional[torch.Tensor] = None, leaves: bool = False, out=None, stream=None):
+    """K20: :func:`gbdt_predict` over the float features ``X`` ``[n, F]`` (float32, float16 or bfloat16) of a forest
+    whose thresholds are uint32 keys (the definition: :func:`mp4x.parallel.gbdt.gbdt_predict_float_torch`): one
+    launch, no bin tensor.  ``out`` is ``pred``, with ``leaves`` the pair ``(pred, leaf)``; ``pred`` may be ``init``."""
+    outs = () if out is None else (out, None) if not leaves else tuple(out)
+    _dev_check(X, nodes, value, tree_off, init, *outs)
+    n, F, T, N = gbdt_args.predict_float(X, nodes, value, tree_off, steps, init)
+    if n >= 2 ** 31 or N >= 2 ** 31 or n * T >= 2 ** 31:
+        raise ValueError("gbdt_predict_float: n, N and n * T must be below 2**31")
+    if nodes.data_ptr() & 15 or value.data_ptr() & 7 or (init is not None and init.data_ptr() & 7):
+        raise ValueError("gbdt_predict_float: nodes must be 16-byte aligned, value and init 8-byte aligned")
+    pred = _gbdt_out("gbdt_predict_float", outs[0] if outs else None, (n,), torch.float64, X.device)
+    leaf = _gbdt_out("gbdt_predict_float", outs[1] if outs else None, (n, T), torch.int32, X.device) if leaves else None
+    if pred.data_ptr() & 7 or (leaf is not None and leaf.data_ptr() & 3):
+        raise ValueError("gbdt_predict_float: pred must be 8-byte aligned and leaf 4-byte aligned")
+    check(native.hip().mp4x_gbdt_predict_float(X.data_ptr() if n else None, int(dtype_of_torch(X.dtype)),
+                                               nodes.data_ptr() if N else None, value.data_ptr() if N else None,
+                                               tree_off.data_ptr(), init.data_ptr() if init is not None and n else None,
+                                               n, F, T, N, steps, pred.data_ptr() if n else None,
+                                               leaf.data_ptr() if leaf is not None and n * T else None,
+                                               stream_ptr(stream)), "mp4x_gbdt_predict_float")
+    return (pred, leaf) if leaves else pred
+
+
 MOE_COMBINE_BWD_MAX_TOP_K = 16       # csrc/kernels/moe.hip: kMoeBwdMaxK
 
 

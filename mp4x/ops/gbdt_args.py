@@ -1,4 +1,4 @@
-"""The argument rules of the fixed-point GBDT ops (K16, K17, K18, K19) and the limits behind them, stated once:
+"""The argument rules of the fixed-point GBDT ops (K16 - K20) and the limits behind them, stated once:
 the definitions of :mod:`mp4x.parallel.gbdt` and the wrappers of :mod:`mp4x.ops.device_ops` both call
 the op's function here, which checks what both forms require and returns the sizes.  What only the
 device requires (GPU tensors, sizes below ``2**31``, alignment, the node caps, ``out=``) stays with the
@@ -78,20 +78,26 @@ def subtract(parent: torch.Tensor, small: torch.Tensor, parent_of: torch.Tensor)
     return parent.shape[0], small.shape[0], parent.shape[1] * parent.shape[2]
 
 
-def predict(bins: torch.Tensor, nodes: torch.Tensor, value: torch.Tensor, tree_off: torch.Tensor, steps: int,
-            init: Optional[torch.Tensor]):
-    """``(n, F, T, N)``; ``init`` may be None (the sums start at ``+0.0``)."""
-    if bins.dtype != torch.uint8 or bins.dim() != 2 or bins.shape[1] < 1:
-        raise ValueError("bins must be uint8 [n, F] with F >= 1")
+def _walk(rows: torch.Tensor, nodes: torch.Tensor, value: torch.Tensor, tree_off: torch.Tensor, steps: int,
+          init: Optional[torch.Tensor]):
+    """``(n, F, T, N)`` of a forest walk over ``rows`` ``[n, F]``, whose own rule the caller has checked."""
     if nodes.dtype != torch.int32 or nodes.dim() != 2 or nodes.shape[1] != 4 or value.dtype != torch.float64 or \
             tuple(value.shape) != (nodes.shape[0],) or tree_off.dtype != torch.int32 or tree_off.dim() != 1 or \
             tree_off.numel() < 1:
         raise ValueError("nodes must be int32 [N, 4], value float64 [N] and tree_off int32 [T + 1]")
     if isinstance(steps, bool) or not isinstance(steps, int) or not 0 <= steps <= MAX_STEPS:
         raise ValueError(f"steps {steps!r} must be an int in [0, {MAX_STEPS}]")
-    if init is not None and (init.dtype != torch.float64 or tuple(init.shape) != (bins.shape[0],)):
+    if init is not None and (init.dtype != torch.float64 or tuple(init.shape) != (rows.shape[0],)):
         raise ValueError("init must be float64 [n]")
-    return tuple(bins.shape) + (tree_off.numel() - 1, nodes.shape[0])
+    return tuple(rows.shape) + (tree_off.numel() - 1, nodes.shape[0])
+
+
+def predict(bins: torch.Tensor, nodes: torch.Tensor, value: torch.Tensor, tree_off: torch.Tensor, steps: int,
+            init: Optional[torch.Tensor]):
+    """``(n, F, T, N)``; ``init`` may be None (the sums start at ``+0.0``)."""
+    if bins.dtype != torch.uint8 or bins.dim() != 2 or bins.shape[1] < 1:
+        raise ValueError("bins must be uint8 [n, F] with F >= 1")
+    return _walk(bins, nodes, value, tree_off, steps, init)
 
 
 def features(X: torch.Tensor):
@@ -99,6 +105,25 @@ def features(X: torch.Tensor):
     if X.dtype not in (torch.float32, torch.float16, torch.bfloat16) or X.dim() != 2:
         raise ValueError("X must be float32, float16 or bfloat16 [n, F]")
     return tuple(X.shape)
+
+
+def predict_float(X: torch.Tensor, nodes: torch.Tensor, value: torch.Tensor, tree_off: torch.Tensor, steps: int,
+                  init: Optional[torch.Tensor]):
+    """``(n, F, T, N)`` of the walk over float features (K20): :func:`predict`'s rules with ``X`` for ``bins``."""
+    if features(X)[1] < 1:
+        raise ValueError("X must have F >= 1 features")
+    return _walk(X, nodes, value, tree_off, steps, init)
+
+
+def float_forest(nodes: torch.Tensor, edges: torch.Tensor, cnt: torch.Tensor):
+    """``(F, E)`` of the edges a forest's bin thresholds are turned into keys with."""
+    if nodes.dtype != torch.int32 or nodes.dim() != 2 or nodes.shape[1] != 4:
+        raise ValueError("nodes must be int32 [N, 4]")
+    if edges.dtype != torch.float32 or edges.dim() != 2 or edges.shape[0] < 1 or edges.shape[1] > MAX_EDGES:
+        raise ValueError(f"edges must be float32 [F, E] with F >= 1 and E <= {MAX_EDGES}")
+    if cnt.dtype != torch.int32 or tuple(cnt.shape) != (edges.shape[0],):
+        raise ValueError("cnt must be int32 [F]")
+    return tuple(edges.shape)
 
 
 def edges(X: torch.Tensor, B: int):

@@ -1,6 +1,6 @@
 """Histogram GBDT in exact fixed point (K16, K17), the forest walk that applies a trained model (K18), the
-binning of float features that both start from (K19): the definitions in torch (also the CPU form) and the
-data-parallel trainer on them.
+binning of float features that both start from (K19) and the walk over float features that needs no bins
+(K20): the definitions in torch (also the CPU form) and the data-parallel trainer on them.
 
 Gradients and hessians are quantised once a tree to int32 with a shift both sides agree on
 (:func:`gbdt_shift` of the job-wide largest magnitude), histograms are int64 sums of them and the
@@ -257,12 +257,19 @@ def gbdt_predict_torch(bins: torch.Tensor, forest: GbdtForest, init: Optional[to
     The order of the sum is fixed, so this form, the kernel and ``sum(tree.predict_bins(...))`` in tree order
     agree bit for bit.  ``out`` receives ``pred`` (the pair ``(pred, leaf)`` with ``leaves``); ``pred`` may be
     ``init``."""
-    n, F, T, N = gbdt_args.predict(bins, forest.nodes, forest.value, forest.tree_off, forest.steps, init)
+    gbdt_args.predict(bins, forest.nodes, forest.value, forest.tree_off, forest.steps, init)
     if bins.is_cuda:
         from ..ops import device_ops
         return device_ops.gbdt_predict(bins.contiguous(), forest.nodes.contiguous(), forest.value.contiguous(),
                                        forest.tree_off.contiguous(), forest.steps,
                                        None if init is None else init.contiguous(), leaves=leaves, out=out)
+    return _walk_torch(bins, forest.nodes[:, 1].to(torch.int64), forest, init, leaves, out)
+
+
+def _walk_torch(cols: torch.Tensor, thr_of: torch.Tensor, forest: GbdtForest, init, leaves: bool, out):
+    """The walk both definitions share, on the CPU: ``cols`` ``[n, F]`` holds integers, ``thr_of`` int64 ``[N]``, and at
+    an inner node a row moves right iff ``int(cols[r, feature]) > thr_of[node]``."""
+    (n, F), T, N = cols.shape, forest.tree_off.numel() - 1, forest.value.numel()
     o = _clamped_bounds(forest.tree_off, N)
     pred = torch.zeros(n, dtype=torch.float64) if init is None else init.clone()
     leaf = torch.full((n, T), -1, dtype=torch.int32)
@@ -270,11 +277,12 @@ def gbdt_predict_torch(bins: torch.Tensor, forest: GbdtForest, init: Optional[to
         size = o[t + 1] - o[t]
         if size == 0:
             continue
-        f, thr, left, right = forest.nodes[o[t]:o[t + 1]].to(torch.int64).unbind(1)
+        f, _, left, right = forest.nodes[o[t]:o[t + 1]].to(torch.int64).unbind(1)
+        thr = thr_of[o[t]:o[t + 1]]
         inner = (f >= 0) & (f < F) & (left >= 0) & (left < size) & (right >= 0) & (right < size)
         j = torch.zeros(n, dtype=torch.int64)
         for _ in range(forest.steps):
-            b = bins.gather(1, torch.where(inner, f, torch.zeros_like(f))[j][:, None])[:, 0].to(torch.int64)
+            b = cols.gather(1, torch.where(inner, f, torch.zeros_like(f))[j][:, None])[:, 0].to(torch.int64)
             j = torch.where(inner[j], torch.where(b > thr[j], right[j], left[j]), j)
         pred = pred + forest.value[o[t]:o[t + 1]][j]
         leaf[:, t] = j.to(torch.int32)
@@ -287,9 +295,88 @@ def gbdt_predict_torch(bins: torch.Tensor, forest: GbdtForest, init: Optional[to
     return (pred, leaf) if leaves else pred
 
 
-def predict_gbdt(trees: Sequence[Tree], bins: torch.Tensor, init: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """The sum of the trees' predictions for the rows of ``bins`` uint8 ``[n, F]``, on the device of ``bins``."""
-    return gbdt_predict_torch(bins, pack_forest(trees, bins.device), init=init)
+def predict_gbdt(trees: Sequence[Tree], bins: torch.Tensor, init: Optional[torch.Tensor] = None,
+                 edges=None) -> torch.Tensor:
+    """The sum of the trees' predictions for the rows of ``bins`` uint8 ``[n, F]``, on the device of ``bins``.  With
+    ``edges=(edges, cnt)``, those the bins of the training rows were made with, ``bins`` is instead the float features
+    ``X`` ``[n, F]`` themselves: the thresholds become keys (:func:`float_forest`) and the rows are walked as they are
+    (:func:`gbdt_predict_float_torch`), which gives what binning them first would, bit for bit."""
+    forest = pack_forest(trees, bins.device)
+    if edges is None:
+        return gbdt_predict_torch(bins, forest, init=init)
+    e, c = edges
+    return gbdt_predict_float_torch(bins, float_forest(forest, e.to(bins.device), c.to(bins.device)), init=init)
+
+
+# ---------------------------------------------------------------- the forest walk over float features (K20)
+_NAN_KEY = 0xfffffffe                 # kNanKey (gbdt_fwalk_map.hpp): the key of a NaN row, above every other row's
+_NEVER = 0xffffffff
+
+
+def _ukeys(x: torch.Tensor) -> torch.Tensor:
+    """``key`` of csrc/kernels/gbdt_bin_map.hpp for float32 values, as int64 in ``[0, 2**32)``: unsigned order is the
+    IEEE order of the non-NaN values, ``-0.0`` takes the key of ``+0.0``; a NaN takes ``_NAN_KEY``.  Bit operations
+    only."""
+    u = x.contiguous().view(torch.int32).to(torch.int64) & 0xffffffff
+    u = torch.where(u == 0x80000000, torch.zeros_like(u), u)
+    k = torch.where(u >= 0x80000000, u ^ 0xffffffff, u | 0x80000000)
+    return torch.where((u & 0x7fffffff) > 0x7f800000, torch.full_like(u, _NAN_KEY), k)
+
+
+def float_forest(forest: GbdtForest, edges: torch.Tensor, cnt: torch.Tensor) -> GbdtForest:
+    """``forest`` with every bin threshold replaced by a uint32 key ``K`` (kept as its int32 bits) that
+    :func:`gbdt_predict_float_torch` compares the keys of float features with: for rows binned by
+    :func:`gbdt_bin_torch` under ``edges`` float32 ``[F, E]`` and ``cnt`` int32 ``[F]`` with ``missing = 255``, the walk of
+    the float rows through the result ends where the walk of their bins through ``forest`` does.  With ``f, t`` a
+    node's feature and threshold and ``c = clamp(cnt[f], 0, E)``::
+
+        t < 0          K = 0                      everyone goes right
+        0 <= t < c     K = key(edges[f, t])       NaN rows, and rows with edges[f, t] <= x
+        c <= t < 255   K = 0xfffffffe             only a NaN row (its bin is 255)
+        t >= 255       K = 0xffffffff             nobody
+        f outside [0, F)   K = 0xffffffff         (the node is never inner)
+
+    For non-decreasing non-NaN edges a row's bin is the number of ``e < c`` with ``edges[f, e] <= x``, so ``bin > t``
+    iff ``t < 0`` or (``t < c`` and ``edges[f, t] <= x``); ValueError if ``edges[f, :c]`` of a feature some node names
+    holds a NaN or descends (:func:`gbdt_edges` gives neither).  ``value``, ``tree_off`` and ``steps`` are the
+    forest's own.  Torch on the forest's device, once a model."""
+    F, E = gbdt_args.float_forest(forest.nodes, edges, cnt)
+    f, t = forest.nodes[:, 0].to(torch.int64), forest.nodes[:, 1].to(torch.int64)
+    named = (f >= 0) & (f < F)
+    c_of = cnt.clamp(0, E).to(torch.int64)
+    used = torch.zeros(F, dtype=torch.bool, device=edges.device)
+    used[f[named]] = True
+    inside = (torch.arange(E, device=edges.device)[None, :] < c_of[:, None]) & used[:, None]
+    if bool((edges.isnan() & inside).any()) or bool(((edges[:, 1:] < edges[:, :-1]) & inside[:, 1:]).any()):
+        raise ValueError("edges[f, :cnt[f]] of a feature the forest names holds a NaN or is not non-decreasing")
+    fc = f.clamp(0, F - 1)
+    c = c_of[fc]
+    edge_key = _ukeys(edges[fc, t.clamp(0, E - 1)]) if E else torch.zeros_like(t)
+    K = torch.where(t < 0, torch.zeros_like(t), torch.where(
+        t < c, edge_key, torch.where(t < 255, torch.full_like(t, _NAN_KEY), torch.full_like(t, _NEVER))))
+    K = torch.where(named, K, torch.full_like(K, _NEVER))
+    nodes = forest.nodes.clone()
+    nodes[:, 1] = torch.where(K >= 2 ** 31, K - 2 ** 32, K).to(torch.int32)
+    return GbdtForest(nodes, forest.value, forest.tree_off, forest.steps)
+
+
+def gbdt_predict_float_torch(X: torch.Tensor, fforest: GbdtForest, init: Optional[torch.Tensor] = None,
+                             leaves: bool = False, out=None):
+    """:func:`gbdt_predict_torch` over the float features ``X`` ``[n, F]`` (float32, or float16 / bfloat16 widened to
+    float32, which is exact; contiguous on the GPU) and a forest of :func:`float_forest`: the same tree table,
+    ``is_inner`` rule, ``steps`` steps, float64 sums in tree order, ``init``, ``out`` and ``leaves``.  The one change is
+    the step: with ``K`` the node's second field read as uint32 and ``xkey`` the key of ``X[r, feature]`` (``key`` of
+    csrc/kernels/gbdt_bin_map.hpp for a non-NaN value, ``0xfffffffe`` for a NaN), the row moves right iff ``K <=
+    xkey``.  Any bits are legal in the forest and in ``X``.  One launch on the GPU and no bin tensor."""
+    gbdt_args.predict_float(X, fforest.nodes, fforest.value, fforest.tree_off, fforest.steps, init)
+    if X.is_cuda:
+        from ..ops import device_ops
+        return device_ops.gbdt_predict_float(X, fforest.nodes.contiguous(), fforest.value.contiguous(),
+                                             fforest.tree_off.contiguous(), fforest.steps,
+                                             None if init is None else init.contiguous(), leaves=leaves, out=out)
+    # K <= xkey iff xkey > K - 1 in integers
+    return _walk_torch(_ukeys(X.to(torch.float32)), (fforest.nodes[:, 1].to(torch.int64) & 0xffffffff) - 1, fforest,
+                       init, leaves, out)
 
 
 # ---------------------------------------------------------------- feature binning (K19)
