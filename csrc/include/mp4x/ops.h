@@ -445,6 +445,22 @@ int mp4x_gbdt_predict_float(const void* X, int dtype, const int32_t* nodes, cons
                             const int32_t* tree_off, const double* init, int64_t n, int64_t F, int64_t T, int64_t N,
                             int steps, double* pred, int32_t* leaf, void* stream);
 
+// ---------------------------------------------------------------- K21 GBDT losses: fused gradient and quantise
+// The (g, h) of a loss from the margins, never stored as floats (csrc/kernels/gbdt_loss_map.hpp holds the rules:
+// every step one f64 operation rounded once, an exp written out, one rounding to f32).  loss 0 squared: g =
+// f32(x - y), h = 1; 1 logistic: p = sigmoid(x), g = f32(p - y), h = f32(p (1 - p)); 2 softmax over C classes:
+// p = softmax of the row, g_c = f32(p_c - [y == c]), h_c = f32(p_c (1 - p_c)), a label outside [0, C) gives +0
+// throughout.  pred f64[C, n] class-major, 16-byte aligned; y f64[n], for softmax int64[n], 8-byte aligned; C
+// = 1 unless softmax, 1 <= C <= 64, 0 <= n < 2^31, else MP4X_E_BADARG before any launch.
+// absmax: top f32[C, 2] = per class the g and the h of the largest key = bits & 0x7fffffff (any NaN above inf),
+// zeroed by a kernel of the same call, then integer maxima only: a function of the input.  n == 0 only zeroes.
+// quantize: gh int32[C, n, 2], 16-byte aligned, gh[c, r] = (q(g, sg[c]), q(h, sh[c])) with q of
+// mp4x_gbdt_quantize; sg, sh int32[C] in device memory, read there only, a value outside +-200 is clamped.  n
+// == 0 launches nothing.  No float atomics, no allocation and no host read: recordable in a graph.
+int mp4x_gbdt_grad_absmax(const double* pred, const void* y, int64_t n, int C, int loss, float* top, void* stream);
+int mp4x_gbdt_grad_quantize(const double* pred, const void* y, int64_t n, int C, int loss, const int32_t* sg,
+                            const int32_t* sh, int32_t* gh, void* stream);
+
 // ---------------------------------------------------------------- errors
 // Reads and clears this thread's last HIP error.  mp4x reports its own failures through return
 // codes; a failed HIP call must not stay "last error" for PyTorch's next kernel-launch check to

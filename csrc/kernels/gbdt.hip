@@ -34,15 +34,6 @@ namespace gm = gbdt_map;
 static_assert(gm::kWaves * gm::kWave == kBlock, "a block is kWaves waves");
 
 constexpr int kGbdtUnroll = 4;        // rows a lane gathers before it uses the first
-constexpr int32_t kGbdtQMax = 2147483647;
-
-__device__ __forceinline__ int32_t gbdt_q(float x, int s) {
-  const double v = __builtin_rint(__builtin_ldexp((double)x, s));   // |s| <= 200: no overflow, no underflow
-  if (v != v) return 0;
-  if (v >= (double)kGbdtQMax) return kGbdtQMax;
-  if (v <= -(double)kGbdtQMax) return -kGbdtQMax;
-  return (int32_t)v;
-}
 
 __global__ __launch_bounds__(kBlock) void k_gbdt_quantize(const float* __restrict__ g, const float* __restrict__ h,
                                                           int64_t n, int sg, int sh, int32_t* __restrict__ gh) {
@@ -50,15 +41,15 @@ __global__ __launch_bounds__(kBlock) void k_gbdt_quantize(const float* __restric
   if (r + 1 < n) {
     const float2 gv = *reinterpret_cast<const float2*>(g + r), hv = *reinterpret_cast<const float2*>(h + r);
     int4 o;
-    o.x = gbdt_q(gv.x, sg);
-    o.y = gbdt_q(hv.x, sh);
-    o.z = gbdt_q(gv.y, sg);
-    o.w = gbdt_q(hv.y, sh);
+    o.x = gm::q(gv.x, sg);
+    o.y = gm::q(hv.x, sh);
+    o.z = gm::q(gv.y, sg);
+    o.w = gm::q(hv.y, sh);
     *reinterpret_cast<int4*>(gh + 2 * r) = o;
   } else if (r < n) {
     int2 o;
-    o.x = gbdt_q(g[r], sg);
-    o.y = gbdt_q(h[r], sh);
+    o.x = gm::q(g[r], sg);
+    o.y = gm::q(h[r], sh);
     *reinterpret_cast<int2*>(gh + 2 * r) = o;
   }
 }

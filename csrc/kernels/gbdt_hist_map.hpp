@@ -49,6 +49,17 @@ constexpr int kMaxShift = 200;                   // |s|: float64(x) * 2**s stays
 constexpr int kLdsBytes = 32768;                 // private histogram a block: fg * B * 16 bytes
 constexpr int64_t kMaxRows = (int64_t)1 << 31;   // m, n < this: slots and rows are 32-bit
 
+constexpr int32_t kQMax = 2147483647;            // a quantised value is clamped to +-kQMax
+
+// The quantiser: rint(f64(x) * 2^s), half to even, NaN -> 0, clamped.  |s| <= kMaxShift: the product is exact.
+MP4X_GBDT_HD int32_t q(float x, int s) {
+  const double v = __builtin_rint(__builtin_ldexp((double)x, s));
+  if (v != v) return 0;
+  if (v >= (double)kQMax) return kQMax;
+  if (v <= -(double)kQMax) return -kQMax;
+  return (int32_t)v;
+}
+
 MP4X_GBDT_HD int64_t min64(int64_t a, int64_t b) { return a < b ? a : b; }
 MP4X_GBDT_HD int64_t max64(int64_t a, int64_t b) { return a > b ? a : b; }
 

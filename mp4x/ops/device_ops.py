@@ -879,6 +879,45 @@ def gbdt_predict_float(X: torch.Tensor, nodes: torch.Tensor, value: torch.Tensor
     return (pred, leaf) if leaves else pred
 
 
+def _gbdt_grad(fn: str, pred: torch.Tensor, y: torch.Tensor, loss: str, tensors) -> Tuple[int, int]:
+    """``(n, C)`` of a K21 call: gbdt_args' rules, then the device's own."""
+    _dev_check(pred, y, *tensors)
+    n, C = gbdt_args.grad(pred, y, loss)
+    if n >= 2 ** 31 or not pred.is_contiguous() or pred.data_ptr() & 15:
+        raise ValueError(f"{fn}: n must be below 2**31 and pred contiguous and 16-byte aligned")
+    return n, C
+
+
+def gbdt_grad_absmax(pred: torch.Tensor, y: torch.Tensor, loss: str, out: Optional[torch.Tensor] = None,
+                     stream=None) -> torch.Tensor:
+    """K21: ``top`` float32 ``[C, 2]``, per class the ``g`` and the ``h`` of the largest magnitude key (``bits &
+    0x7fffffff``: any NaN above infinity) of the loss's gradients, none of which is stored (the definition:
+    :func:`mp4x.parallel.gbdt.gbdt_grad_absmax_torch`).  ``out`` is zeroed by the call."""
+    n, C = _gbdt_grad("gbdt_grad_absmax", pred, y, loss, (out,))
+    out = _gbdt_out("gbdt_grad_absmax", out, (C, 2), torch.float32, pred.device)
+    check(native.hip().mp4x_gbdt_grad_absmax(pred.data_ptr() if n else None, y.data_ptr() if n else None, n, C,
+                                             gbdt_args.LOSSES.index(loss), out.data_ptr(), stream_ptr(stream)),
+          "mp4x_gbdt_grad_absmax")
+    return out
+
+
+def gbdt_grad_quantize(pred: torch.Tensor, y: torch.Tensor, loss: str, sg: torch.Tensor, sh: torch.Tensor,
+                       out: Optional[torch.Tensor] = None, stream=None) -> torch.Tensor:
+    """K21: ``gh`` int32 ``[C, n, 2]``, the loss's gradients quantised with class c's shifts ``sg[c]``, ``sh[c]`` (int32
+    ``[C]`` on the device, read there only; a value outside ``+-200`` is clamped) without a float gradient in memory
+    (the definition: :func:`mp4x.parallel.gbdt.gbdt_grad_quantize_torch`)."""
+    n, C = _gbdt_grad("gbdt_grad_quantize", pred, y, loss, (sg, sh, out))
+    gbdt_args.grad_shifts(sg, sh, C)
+    out = _gbdt_out("gbdt_grad_quantize", out, (C, n, 2), torch.int32, pred.device)
+    if n and out.data_ptr() & 15:
+        raise ValueError("gbdt_grad_quantize: out must be 16-byte aligned")
+    check(native.hip().mp4x_gbdt_grad_quantize(pred.data_ptr() if n else None, y.data_ptr() if n else None, n, C,
+                                               gbdt_args.LOSSES.index(loss), sg.data_ptr(), sh.data_ptr(),
+                                               out.data_ptr() if n else None, stream_ptr(stream)),
+          "mp4x_gbdt_grad_quantize")
+    return out
+
+
 MOE_COMBINE_BWD_MAX_TOP_K = 16       # csrc/kernels/moe.hip: kMoeBwdMaxK
 
 

@@ -1,4 +1,4 @@
-"""The argument rules of the fixed-point GBDT ops (K16 - K20) and the limits behind them, stated once:
+"""The argument rules of the fixed-point GBDT ops (K16 - K21) and the limits behind them, stated once:
 the definitions of :mod:`mp4x.parallel.gbdt` and the wrappers of :mod:`mp4x.ops.device_ops` both call
 the op's function here, which checks what both forms require and returns the sizes.  What only the
 device requires (GPU tensors, sizes below ``2**31``, alignment, the node caps, ``out=``) stays with the
@@ -17,6 +17,8 @@ MAX_BINS = 256                       # kMaxBins: bins are bytes
 QMAX = 2 ** 31 - 1                   # a quantised gradient or hessian is clamped to +-QMAX
 MAX_STEPS = 64                       # kMaxSteps (gbdt_walk_map.hpp): the longest root-to-leaf path, in edges
 MAX_EDGES = 255                      # kMaxEdges (gbdt_bin_map.hpp): a position among the edges is a byte
+MAX_CLASSES = 64                     # kMaxClasses (gbdt_loss_map.hpp): a block's key table is 2 * 64 words
+LOSSES = ("squared", "logistic", "softmax")      # a loss's code in the native calls is its index
 
 
 def shifts(*s) -> None:
@@ -143,3 +145,27 @@ def bin(X: torch.Tensor, edges: torch.Tensor, cnt: torch.Tensor, missing: int):
     if isinstance(missing, bool) or not isinstance(missing, int) or not 0 <= missing <= 255:
         raise ValueError(f"missing {missing!r} must be an int in [0, 255]")
     return X.shape[0], F, edges.shape[1]
+
+
+def grad(pred: torch.Tensor, y: torch.Tensor, loss: str, classes: Optional[int] = None):
+    """``(n, C)`` of the margins of a loss (K21): ``pred`` float64 ``[n]`` and ``y`` float64 ``[n]``, or for
+    ``"softmax"`` ``pred`` float64 ``[C, n]`` class-major, ``1 <= C <= MAX_CLASSES``, and ``y`` int64 ``[n]``.  ``classes``
+    may be given with ``"softmax"`` alone and is then ``C``."""
+    if loss not in LOSSES:
+        raise ValueError(f"loss {loss!r} must be one of {LOSSES}")
+    soft = loss == "softmax"
+    if classes is not None and (not soft or isinstance(classes, bool) or not isinstance(classes, int)):
+        raise ValueError(f"classes {classes!r} goes with loss='softmax' alone and is an int")
+    if pred.dtype != torch.float64 or pred.dim() != (2 if soft else 1):
+        raise ValueError("pred must be float64 [n], for softmax float64 [C, n]")
+    n, C = pred.shape[-1], pred.shape[0] if soft else 1
+    if not 1 <= C <= MAX_CLASSES or classes not in (None, C):
+        raise ValueError(f"pred holds {C} classes: at least 1, at most {MAX_CLASSES}, and classes={classes!r} if given")
+    if y.dtype != (torch.int64 if soft else torch.float64) or tuple(y.shape) != (n,):
+        raise ValueError("y must be float64 [n], for softmax int64 [n]")
+    return n, C
+
+
+def grad_shifts(sg: torch.Tensor, sh: torch.Tensor, C: int) -> None:
+    if any(s.dtype != torch.int32 or tuple(s.shape) != (C,) for s in (sg, sh)):
+        raise ValueError("sg and sh must be int32 [C]")

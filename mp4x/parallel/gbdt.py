@@ -1,6 +1,7 @@
 """Histogram GBDT in exact fixed point (K16, K17), the forest walk that applies a trained model (K18), the
-binning of float features that both start from (K19) and the walk over float features that needs no bins
-(K20): the definitions in torch (also the CPU form) and the data-parallel trainer on them.
+binning of float features that both start from (K19), the walk over float features that needs no bins
+(K20) and the classification losses with their fused gradient ops (K21): the definitions in torch (also the
+CPU form) and the data-parallel trainer on them.
 
 Gradients and hessians are quantised once a tree to int32 with a shift both sides agree on
 (:func:`gbdt_shift` of the job-wide largest magnitude), histograms are int64 sums of them and the
@@ -296,11 +297,18 @@ def _walk_torch(cols: torch.Tensor, thr_of: torch.Tensor, forest: GbdtForest, in
 
 
 def predict_gbdt(trees: Sequence[Tree], bins: torch.Tensor, init: Optional[torch.Tensor] = None,
-                 edges=None) -> torch.Tensor:
+                 edges=None, classes: Optional[int] = None) -> torch.Tensor:
     """The sum of the trees' predictions for the rows of ``bins`` uint8 ``[n, F]``, on the device of ``bins``.  With
     ``edges=(edges, cnt)``, those the bins of the training rows were made with, ``bins`` is instead the float features
     ``X`` ``[n, F]`` themselves: the thresholds become keys (:func:`float_forest`) and the rows are walked as they are
-    (:func:`gbdt_predict_float_torch`), which gives what binning them first would, bit for bit."""
+    (:func:`gbdt_predict_float_torch`), which gives what binning them first would, bit for bit.  With ``classes=C``
+    the trees are round-major as ``train_gbdt_quantized(loss="softmax")`` returns them and the result is the
+    margins float64 ``[C, n]``: class c is this call over ``trees[c::C]`` (``init`` float64 ``[C, n]``)."""
+    if classes is not None:
+        if isinstance(classes, bool) or not isinstance(classes, int) or classes < 1 or len(trees) % classes:
+            raise ValueError(f"classes {classes!r} must be an int >= 1 that divides the {len(trees)} trees")
+        return torch.stack([predict_gbdt(trees[c::classes], bins, None if init is None else init[c], edges)
+                            for c in range(classes)])
     forest = pack_forest(trees, bins.device)
     if edges is None:
         return gbdt_predict_torch(bins, forest, init=init)
@@ -483,6 +491,109 @@ def fit_bins(comm, X: torch.Tensor, B: int, missing: int = 255):
     return gbdt_bin_torch(X, edges, cnt, missing), edges, cnt
 
 
+# ---------------------------------------------------------------- losses (K21)
+_LN2_HI, _LN2_LO = float.fromhex("0x1.62e42fee00000p-1"), float.fromhex("0x1.a39ef35793c76p-33")
+_INV_LN2 = float.fromhex("0x1.71547652b82fep+0")
+_EXP_C = [1.0 / math.factorial(j) for j in range(14)]      # int / int is rounded once: the nearest float64 of 1 / j!
+_CLAMP = 708.0
+
+
+def _exp_neg(t: torch.Tensor) -> torch.Tensor:
+    """``exp_neg`` of csrc/kernels/gbdt_loss_map.hpp, operation for operation: ``exp(-t)`` for float64 ``t`` in ``[0,
+    708]``, a NaN staying itself."""
+    nan = t.isnan()
+    x = -torch.where(nan, torch.zeros_like(t), t)
+    k = torch.round(x * _INV_LN2)
+    r = (x - k * _LN2_HI) - k * _LN2_LO
+    p = torch.full_like(r, _EXP_C[13])
+    for c in _EXP_C[12::-1]:
+        p = p * r
+        p = p + c
+    scale = ((k.to(torch.int64) + 1023) << 52).view(torch.float64)
+    return torch.where(nan, t, p * scale)
+
+
+def _clamp_t(t: torch.Tensor) -> torch.Tensor:
+    return torch.where(t > _CLAMP, torch.full_like(t, _CLAMP), t)          # a NaN passes
+
+
+def gbdt_grad_torch(pred: torch.Tensor, y: torch.Tensor, loss: str = "squared"):
+    """``(g, h)`` float32 of ``pred``'s shape: the gradient and the hessian of ``loss`` at the margins ``pred``.  The
+    definition of K21: every step is one float64 operation rounded once, then one rounding to float32 - no library
+    ``exp`` - and csrc/kernels/gbdt_loss_map.hpp is the same steps in C++, so the CPU, the GPU and any rank count
+    give the same bits.
+
+    ``"squared"``: ``pred``, ``y`` float64 ``[n]``; ``g = float32(pred - y)``, ``h = 1``.
+
+    ``"logistic"``: the same shapes, ``y`` any float64.  ``e = exp_neg(min(|x|, 708))``, ``d = 1 + e``, ``p = 1 / d`` if
+    ``x >= 0`` else ``e / d`` and ``q`` the other quotient; ``g = float32(p - y)``, ``h = float32(p * q)``.  A NaN ``x`` gives
+    NaN ``g`` and ``h`` (which quantise to 0).
+
+    ``"softmax"``: ``pred`` float64 ``[C, n]`` class-major, ``y`` int64 ``[n]`` class ids.  ``m = max_c x_c``, ``e_c =
+    exp_neg(min(m - x_c, 708))``, ``S`` their sum in class order, ``p_c = e_c / S``; ``g_c = float32(p_c - [y == c])``,
+    ``h_c = float32(p_c * (1 - p_c))``.  A row with a NaN or ``+inf`` margin is NaN throughout; a label outside ``[0,
+    C)`` makes the row's ``2C`` outputs ``+0``: the row is ignored."""
+    n, C = gbdt_args.grad(pred, y, loss)
+    if loss == "squared":
+        return (pred - y).to(torch.float32), torch.ones(n, dtype=torch.float32, device=pred.device)
+    if loss == "logistic":
+        e = _exp_neg(_clamp_t(pred.abs()))
+        d = e + 1.0
+        a, b = torch.ones_like(d) / d, e / d
+        up = pred >= 0
+        p, q = torch.where(up, a, b), torch.where(up, b, a)
+        return (p - y).to(torch.float32), (p * q).to(torch.float32)
+    m = pred[0]
+    for c in range(1, C):
+        x = pred[c]
+        m = torch.where(m.isnan(), m, torch.where(x.isnan() | (x > m), x, m))
+    e = [_exp_neg(_clamp_t(m - pred[c])) for c in range(C)]
+    S = e[0]
+    for c in range(1, C):
+        S = S + e[c]
+    live = (y >= 0) & (y < C)
+    g, h = [], []
+    for c in range(C):
+        p = e[c] / S
+        g.append(torch.where(live, p - (y == c).to(torch.float64), torch.zeros_like(p)))
+        h.append(torch.where(live, p * (1.0 - p), torch.zeros_like(p)))
+    return torch.stack(g).to(torch.float32), torch.stack(h).to(torch.float32)
+
+
+def _give(result: torch.Tensor, out: Optional[torch.Tensor]) -> torch.Tensor:
+    return result if out is None else out.copy_(result)
+
+
+def gbdt_grad_absmax_torch(pred: torch.Tensor, y: torch.Tensor, loss: str, out: torch.Tensor = None) -> torch.Tensor:
+    """``top`` float32 ``[C, 2]``: per class the ``g`` and the ``h`` of :func:`gbdt_grad_torch` with the largest key ``bits
+    & 0x7fffffff`` - ``abs().max()`` with any NaN above infinity, 0 for ``n = 0``.  An integer maximum: the order of the
+    rows cannot show.  On GPU tensors one call that stores no gradient."""
+    n, C = gbdt_args.grad(pred, y, loss)
+    if pred.is_cuda:
+        from ..ops import device_ops
+        return device_ops.gbdt_grad_absmax(pred, y, loss, out=out)
+    keys = torch.stack([x.reshape(C, n).contiguous().view(torch.int32) & 0x7fffffff
+                        for x in gbdt_grad_torch(pred, y, loss)], dim=1)                      # [C, 2, n]
+    top = keys.max(dim=2).values if n else torch.zeros(C, 2, dtype=torch.int32)
+    return _give(top.contiguous().view(torch.float32), out)
+
+
+def gbdt_grad_quantize_torch(pred: torch.Tensor, y: torch.Tensor, loss: str, sg: torch.Tensor, sh: torch.Tensor,
+                             out: torch.Tensor = None) -> torch.Tensor:
+    """``gh`` int32 ``[C, n, 2]``: ``gh[c] = gbdt_quantize_torch(g[c], h[c], sg[c], sh[c])`` of :func:`gbdt_grad_torch`'s
+    gradients, ``sg``, ``sh`` int32 ``[C]`` on the device of ``pred`` (a value outside ``+-MAX_SHIFT`` is clamped).  On GPU
+    tensors one call in which the float gradients never reach memory and the shifts are read on the device."""
+    n, C = gbdt_args.grad(pred, y, loss)
+    gbdt_args.grad_shifts(sg, sh, C)
+    if pred.is_cuda:
+        from ..ops import device_ops
+        return device_ops.gbdt_grad_quantize(pred, y, loss, sg, sh, out=out)
+    g, h = (x.reshape(C, n) for x in gbdt_grad_torch(pred, y, loss))
+    s = torch.stack([sg, sh]).clamp(-MAX_SHIFT, MAX_SHIFT).tolist()
+    gh = torch.stack([gbdt_quantize_torch(g[c], h[c], s[0][c], s[1][c]) for c in range(C)])
+    return _give(gh, out)
+
+
 # ---------------------------------------------------------------- the trainer
 def _allreduce(comm, t: torch.Tensor, operand, operator) -> torch.Tensor:
     """In-place allreduce of a flat tensor over the job: the device engine for a GPU tensor, the host
@@ -632,9 +743,43 @@ class _PartitionLevels(_Levels):
         self.seg = seg2[torch.tensor(take).to(dev)]
 
 
+def _check_modes(level: str, subtract: bool, update: str) -> None:
+    if level not in ("sort", "partition"):
+        raise ValueError(f"level {level!r} must be 'sort' or 'partition'")
+    if subtract and level != "partition":
+        raise ValueError("subtract=True needs level='partition'")
+    if update not in ("rows", "walk"):
+        raise ValueError(f"update {update!r} must be 'rows' or 'walk'")
+    if update == "walk" and level != "partition":
+        raise ValueError("update='walk' needs level='partition'")
+
+
+def _grow_tree(comm, bins, gh, pred, B, sg, sh, depth, lr, lam, level, subtract, update):
+    """``(tree, pred)``: one tree grown level by level on the quantised ``gh`` int32 ``[n, 2]``, and ``pred`` float64
+    ``[n]`` with the tree's values added as ``update`` says (in place for ``"rows"``, a new tensor for ``"walk"``)."""
+    n, dev = bins.shape[0], bins.device
+    levels = _PartitionLevels(comm, bins, gh, B, subtract) if level == "partition" else \
+        _SortLevels(comm, bins, gh, B)
+    node_of = torch.zeros(n, dtype=torch.int64, device=dev) if update == "rows" else None
+    tree = Tree([-1], [-1], [-1], [-1], [0.0])
+    for level_no in range(depth + 1):
+        hist, nodes = levels.histograms(tree, node_of)
+        rec = [t.tolist() for t in gbdt_split_torch(hist, sg, sh, lam)]
+        if not grow_level(tree, nodes, rec, sg, sh, lam, lr, last=level_no == depth):
+            break
+        levels.advance(tree, rec)
+        if update == "rows":
+            node_of = move_rows(bins, node_of, tree, nodes)
+    if update == "rows":
+        pred += torch.tensor(tree.value, dtype=torch.float64, device=dev)[node_of]
+    else:
+        pred = gbdt_predict_torch(bins, pack_forest([tree], dev), init=pred)
+    return tree, pred
+
+
 def train_gbdt_quantized(comm, bins: torch.Tensor, y: torch.Tensor, B: int, trees: int = 5, depth: int = 3,
                          lr: float = 0.3, lam: float = 1.0, level: str = "sort", subtract: bool = False,
-                         update: str = "rows") -> List[Tree]:
+                         update: str = "rows", loss: str = "squared", classes: Optional[int] = None) -> List[Tree]:
     """:func:`mp4x.models.gbdt.train_gbdt` on fixed-point statistics: ``bins`` uint8 ``[n, F]`` and ``y``
     ``[n]`` are this rank's rows, torch tensors on the CPU or the GPU.  Squared loss: ``g = float32(pred -
     y)``, ``h = 1``.  Per tree one allreduce MAX of ``(max|g|, max|h|)`` fixes the shifts and the rows are
@@ -656,15 +801,15 @@ def train_gbdt_quantized(comm, bins: torch.Tensor, y: torch.Tensor, B: int, tree
     (:func:`move_rows`) and adds ``value[node_of]``; ``"walk"`` (``level="partition"`` only, which never reads
     ``node_of``) keeps no ``node_of`` and walks the finished tree once with :func:`gbdt_predict_torch` (K18).  The
     walk ends on the leaf ``node_of`` would hold and adds the same float64, so the trees are the same bit for
-    bit."""
-    if level not in ("sort", "partition"):
-        raise ValueError(f"level {level!r} must be 'sort' or 'partition'")
-    if subtract and level != "partition":
-        raise ValueError("subtract=True needs level='partition'")
-    if update not in ("rows", "walk"):
-        raise ValueError(f"update {update!r} must be 'rows' or 'walk'")
-    if update == "walk" and level != "partition":
-        raise ValueError("update='walk' needs level='partition'")
+    bit.
+
+    ``loss`` is ``"squared"`` (the above), ``"logistic"`` (``y`` in ``[0, 1]``, the trees sum to a log-odds margin) or
+    ``"softmax"`` (``y`` int64 class ids and ``classes=C``, which goes with softmax alone; ``C`` trees a round, returned
+    round-major: tree ``t * C + c`` adds to class c's margin, see :func:`predict_gbdt`).  The last two are
+    :func:`train_gbdt_fused`."""
+    if loss != "squared" or classes is not None:
+        return train_gbdt_fused(comm, bins, y, B, loss, classes, trees, depth, lr, lam, level, subtract, update)
+    _check_modes(level, subtract, update)
     dev = bins.device
     n = bins.shape[0]
     y = y.to(device=dev, dtype=torch.float64)
@@ -678,21 +823,48 @@ def train_gbdt_quantized(comm, bins: torch.Tensor, y: torch.Tensor, B: int, tree
         top = _allreduce(comm, top, Operands.DOUBLE_OPERAND(), Operators.Double.MAX).tolist()
         sg, sh = gbdt_shift(top[0]), gbdt_shift(top[1])
         gh = gbdt_quantize_torch(g, h, sg, sh)
-        levels = _PartitionLevels(comm, bins, gh, B, subtract) if level == "partition" else \
-            _SortLevels(comm, bins, gh, B)
-        node_of = torch.zeros(n, dtype=torch.int64, device=dev) if update == "rows" else None
-        tree = Tree([-1], [-1], [-1], [-1], [0.0])
-        for level_no in range(depth + 1):
-            hist, nodes = levels.histograms(tree, node_of)
-            rec = [t.tolist() for t in gbdt_split_torch(hist, sg, sh, lam)]
-            if not grow_level(tree, nodes, rec, sg, sh, lam, lr, last=level_no == depth):
-                break
-            levels.advance(tree, rec)
-            if update == "rows":
-                node_of = move_rows(bins, node_of, tree, nodes)
-        if update == "rows":
-            pred += torch.tensor(tree.value, dtype=torch.float64, device=dev)[node_of]
-        else:
-            pred = gbdt_predict_torch(bins, pack_forest([tree], dev), init=pred)
+        tree, pred = _grow_tree(comm, bins, gh, pred, B, sg, sh, depth, lr, lam, level, subtract, update)
         out.append(tree)
+    return out
+
+
+def train_gbdt_fused(comm, bins: torch.Tensor, y: torch.Tensor, B: int, loss: str, classes: Optional[int] = None,
+                     trees: int = 5, depth: int = 3, lr: float = 0.3, lam: float = 1.0, level: str = "sort",
+                     subtract: bool = False, update: str = "rows") -> List[Tree]:
+    """:func:`train_gbdt_quantized` for any loss of :func:`gbdt_grad_torch`, over the fused gradient ops (K21): the
+    margins ``pred`` float64 ``[C, n]`` stay class-major on the device of ``bins`` and per round there is one
+    :func:`gbdt_grad_absmax_torch`, one allreduce MAX of its ``2C`` values as doubles (a NaN counts as infinity),
+    :func:`gbdt_shift` per class, one :func:`gbdt_grad_quantize_torch` with the shifts as a device tensor, and then
+    for ``c = 0 .. C - 1`` one tree grown on ``gh[c]`` by the level machinery of :func:`train_gbdt_quantized`, which
+    updates ``pred[c]``.  ``trees`` is the number of rounds; tree ``t * C + c`` of the result is round t's tree of class
+    c.  ``"logistic"`` and ``"squared"`` have ``C = 1``; ``"squared"`` grows the trees of :func:`train_gbdt_quantized`'s
+    default bit for bit.  Every gradient is per row and specified to the bit, every sum is in integers: the trees do
+    not depend on the rank count or the device."""
+    _check_modes(level, subtract, update)
+    if (loss == "softmax") != (classes is not None):
+        raise ValueError("classes is required with loss='softmax' and goes with no other loss")
+    dev, n = bins.device, bins.shape[0]
+    C = classes if loss == "softmax" else 1
+    if isinstance(C, bool) or not isinstance(C, int) or not 1 <= C <= gbdt_args.MAX_CLASSES:
+        raise ValueError(f"classes {C!r} must be an int in [1, {gbdt_args.MAX_CLASSES}]")
+    y = y.to(device=dev, dtype=torch.int64 if loss == "softmax" else torch.float64)
+    pred = torch.zeros((C, n) if loss == "softmax" else (n,), dtype=torch.float64, device=dev)
+    gbdt_args.grad(pred, y, loss, classes)
+    margins = pred.view(C, n)
+    top = torch.empty(C, 2, dtype=torch.float32, device=dev)
+    gh = torch.empty(C, n, 2, dtype=torch.int32, device=dev)
+    out: List[Tree] = []
+    for _ in range(trees):
+        gbdt_grad_absmax_torch(pred, y, loss, out=top)
+        job = torch.nan_to_num(top.double().view(-1), nan=math.inf)
+        job = _allreduce(comm, job, Operands.DOUBLE_OPERAND(), Operators.Double.MAX).tolist()
+        shifts = [[gbdt_shift(job[2 * c + j]) for c in range(C)] for j in (0, 1)]
+        on_dev = torch.tensor(shifts, dtype=torch.int32).to(dev)
+        gbdt_grad_quantize_torch(pred, y, loss, on_dev[0], on_dev[1], out=gh)
+        for c in range(C):
+            tree, moved = _grow_tree(comm, bins, gh[c], margins[c], B, shifts[0][c], shifts[1][c], depth, lr, lam, level,
+                                     subtract, update)
+            if moved.data_ptr() != margins[c].data_ptr():          # update="walk" gives a new tensor
+                margins[c].copy_(moved)
+            out.append(tree)
     return out
